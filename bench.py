@@ -12,6 +12,9 @@ loop-closure descriptor exchange of configs[4]) and matches its first frame agai
 frame read from the gathered descriptors (one step later, so the gather overlaps the next step's
 kernels).
 
+A plain run sets up, warms up, times `--steps` steps, writes the last step's outputs with `--dump-outputs DIR`
+and prints the headline line.  Everything below runs only with `--full`.
+
 Secondary objects on the same JSON line, each with its own rate, roofline and CPU baseline:
   c1          configs[0]: 640x480, 1000 features — GPU batch throughput + the CPU plumbing median of 200
               single-frame Extract calls (seeds 0-15)
@@ -1307,6 +1310,12 @@ def parse_args(argv=None):
     ap.add_argument("--width", type=int, default=1280)
     ap.add_argument("--height", type=int, default=720)
     ap.add_argument("--nfeatures", type=int, default=2000)
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline run also the per-stage pass and rooflines, C5, the secondary legs and the "
+                         "CPU baselines (the --no-* options below select among them)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the last timed step returned (keypoints, descriptors, counts, matches; a fixed "
+                         "sample of frames) as DIR/<name>.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--force-exchange", action="store_true",
                     help="run the N > 1 exchange path (pack, counts / payload gather, cross-shard match) at N = 1 too")
@@ -1351,8 +1360,106 @@ def main():
         m = ORBmatcher(0.6, False)
     run = ShardedRun(ranks, ex, m, base, B, exchange=world > 1 or args.force_exchange)
     # inside the timed region only the dominant kernel (fast_cells) carries launch events (events on every
-    # kernel cost ~3.5 %); the other stages are timed in a separate pass below
+    # kernel cost ~3.5 %); the other stages are timed in a separate pass of --full.  The region is the same with
+    # and without --full, so `value` is one quantity
     elapsed, timed = run.timed(args.steps, args.warmup, profile_stage="fast_cells")
+    if args.dump_outputs and rank == 0:
+        dump_outputs(Path(args.dump_outputs), run, B)
+    sl = run.slots()
+    n_kp = float(sl.counts.float().mean().item())
+    matches = int((run.match_out[3] >= 0).sum().item())
+    value = total * args.steps / elapsed
+    ms_per_step = 1e3 * elapsed / args.steps
+    sb = stage_bytes(W, H, n_kp)
+    # fast_cells against the HBM roofline from the launch events the timed steps already carried
+    fc_ms, fc_launches = timed["fast_cells"]
+    per_launch_ms = fc_ms / max(fc_launches, 1)
+    launches_per_step = fc_launches / max(args.steps, 1)
+    fc_bytes = sb["fast_cells"] * B / max(launches_per_step, 1)
+    achieved = fc_bytes / (per_launch_ms * 1e-3) / 1e9 if per_launch_ms > 0 else 0.0
+
+    result = {
+        "metric": METRIC,
+        "value": value,
+        "unit": "frames/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": ms_per_step,
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "u8",
+        "data": ("STUB (CPU launcher test, no extraction)" if args.stub else
+                 "synthetic (pan sequence of §8d G frames, shifted (+3,+2) px per frame)"),
+        "config": {"workload": f"C2: {W}x{H} mono, 8 levels, {args.nfeatures} features, extract + brute-force "
+                               f"Hamming top-2/ratio match of every frame vs its predecessor",
+                   "frames_per_step": total, "frames_per_step_per_gpu": B, "width": W, "height": H, "nlevels": 8,
+                   "nfeatures": args.nfeatures, "parallelism": f"{total}-frame job sharded over {world} GPU(s), "
+                   f"{B} frames per GPU" + (", RCCL all-gather of the descriptor blocks, cross-shard predecessor match"
+                                          if world > 1 else "")},
+        "roofline": {"bound": "hbm", "kernel": "fast_cells", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                     "frac": achieved / HBM_PEAK_GBS, "algorithmic_bytes_per_launch": fc_bytes,
+                     "avg_launch_ms": per_launch_ms, "launches_per_step": launches_per_step,
+                     "timed_from": "timed region"},
+        "keypoints_per_frame": n_kp,
+        "keypoint_quota": args.nfeatures,
+        "keypoints_over_quota": n_kp / args.nfeatures if args.nfeatures else None,
+        "matches_last_step": matches,
+        "device_fault_mask": run.fault,
+        "timed_region_s": elapsed,
+        "full": bool(args.full),
+    }
+    if args.stub:
+        result["stub"] = True
+    if args.full:
+        full_report(result, args, ranks, run, ex, m, base, timed)
+    if rank == 0:
+        print(json.dumps(result), flush=True)
+    ranks.close()
+
+
+def dump_outputs(out_dir, run, B, max_frames=64, budget=64 << 20):
+    """`--dump-outputs DIR`: what the last timed step handed its caller, as float32 / float64 `.npy` files:
+    the extractor's keypoint slots, descriptors and per-frame counts and the matcher's (best_idx, best,
+    second, match) rows.  The batch is far larger than `budget` bytes, so the slots of a fixed, seeded
+    sample of frames are written (`frame_index.npy` says which; the counts are written for every frame).
+    Slot rows at and past a frame's count were never written by the step and are stored as 0 (matches:
+    -1), as is the match row of local frame 0, which has no in-shard predecessor."""
+    import torch
+    sl = run.slots()
+    cap = int(sl.desc.shape[1])
+    per_frame = cap * (7 + 32 + 4) * 4                       # float32 bytes of one frame's three slot arrays
+    n = max(1, min(B, max_frames, (budget - 12 * B) // per_frame))
+    idx = np.sort(np.random.default_rng(0).choice(B, size=n, replace=False))
+    sel = torch.from_numpy(idx).to(sl.desc.device)
+    counts = sl.counts.cpu().numpy()
+    kps = sl.kps[sel].cpu().numpy()                          # (n, cap, 7) int32 words, orbx_keypoint layout
+    desc = sl.desc[sel].cpu().numpy()
+    mt = run.match_out[:, sel].cpu().numpy()
+    live = np.arange(cap)[None, :] < counts[idx][:, None]    # (n, cap): rows the step wrote
+    kp = np.empty(kps.shape, np.float32)
+    kp[:, :, :5] = np.ascontiguousarray(kps[:, :, :5]).view(np.float32)   # x y size angle response
+    kp[:, :, 5:] = kps[:, :, 5:]                                           # octave class_id
+    kp[~live] = 0
+    d = desc.astype(np.float32)
+    d[~live] = 0
+    mlive = live & (idx > 0)[:, None]
+    mf = np.where(mlive[None], mt, -1).astype(np.float32)
+    out_dir.mkdir(parents=True, exist_ok=True)
+    np.save(out_dir / "frame_index.npy", idx.astype(np.float64))
+    np.save(out_dir / "keypoint_counts.npy", counts.astype(np.float32))
+    np.save(out_dir / "keypoints.npy", kp)
+    np.save(out_dir / "descriptors.npy", d)
+    np.save(out_dir / "matches.npy", mf)
+
+
+def full_report(result, args, ranks, run, ex, m, base, timed):
+    """`--full`: everything beside the headline, added to `result`: the per-stage pass and rooflines of the
+    headline workload, C5, the secondary legs and the CPU baselines."""
+    rank, world = ranks.rank, ranks.world
+    W, H, B = args.width, args.height, args.frames
+    ms_per_step = result["ms_per_step"]
     ex.profile(True)
     for _ in range(3):
         run.step()
@@ -1376,10 +1483,7 @@ def main():
         e1.synchronize()
         match_ms = e0.elapsed_time(e1) / 3
 
-    n_kp = float(sl.counts.float().mean().item())
-    matches = int((run.match_out[3] >= 0).sum().item())
-    value = total * args.steps / elapsed
-    ms_per_step = 1e3 * elapsed / args.steps
+    n_kp = result["keypoints_per_frame"]
     bytes_frame, P = algorithmic_bytes(W, H, n_kp)
     sb = stage_bytes(W, H, n_kp)
     dom = max(breakdown, key=lambda k: breakdown[k][0])
@@ -1396,26 +1500,7 @@ def main():
     pipe_traffic = measured_traffic_step(B, W, H, args.nfeatures)
     match_tflops = 512.0 * n_kp * n_kp * (B - 1) / (match_ms * 1e-3) / 1e12 if match_ms else 0.0
 
-    result = {
-        "metric": METRIC,
-        "value": value,
-        "unit": "frames/s",
-        "n_gpus": world,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": ms_per_step,
-        "higher_is_better": True,
-        "scaling": "weak",
-        "vs_baseline": None,
-        "dtype": "u8",
-        "data": ("STUB (CPU launcher test, no extraction)" if args.stub else
-                 "synthetic (pan sequence of §8d G frames, shifted (+3,+2) px per frame)"),
-        "config": {"workload": f"C2: {W}x{H} mono, 8 levels, {args.nfeatures} features, extract + brute-force "
-                               f"Hamming top-2/ratio match of every frame vs its predecessor",
-                   "frames_per_step": total, "frames_per_step_per_gpu": B, "width": W, "height": H, "nlevels": 8,
-                   "nfeatures": args.nfeatures, "parallelism": f"{total}-frame job sharded over {world} GPU(s), "
-                   f"{B} frames per GPU" + (", RCCL all-gather of the descriptor blocks, cross-shard predecessor match"
-                                          if world > 1 else "")},
+    result.update({
         "roofline": {"bound": "hbm", "kernel": dom, "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
                      "frac": achieved / HBM_PEAK_GBS, "traffic": traffic,
                      "algorithmic_bytes_per_launch": dom_bytes, "avg_launch_ms": per_launch_ms,
@@ -1440,15 +1525,7 @@ def main():
                            "peak": FP4_PEAK_TFLOPS, "unit": "TFLOP/s (FP4)", "frac": match_tflops / FP4_PEAK_TFLOPS,
                            "ops": "512 FP4 flops per query x candidate pair, n_kp^2 pairs per matched frame (B - 1 per step)",
                            "match_ms_per_step": match_ms},
-        "keypoints_per_frame": n_kp,
-        "keypoint_quota": args.nfeatures,
-        "keypoints_over_quota": n_kp / args.nfeatures if args.nfeatures else None,
-        "matches_last_step": matches,
-        "device_fault_mask": run.fault,
-        "timed_region_s": elapsed,
-    }
-    if args.stub:
-        result["stub"] = True
+    })
     if run.xchg is not None:
         result["exchange"] = dict(run.exchange_block(args.steps),
                                   workload="the headline's exchange (weak scaling, frames_per_step_per_gpu per rank)")
@@ -1505,9 +1582,6 @@ def main():
     # the metric's other halves, flat and last on the line (a record that keeps only the tail of stdout
     # still holds them)
     result["summary"] = summary(result)
-    if rank == 0:
-        print(json.dumps(result), flush=True)
-    ranks.close()
 
 
 def summary(r):

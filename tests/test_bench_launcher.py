@@ -33,7 +33,8 @@ def _run(args, env, timeout=240):
 
 
 def test_launcher_starts_n_ranks_stub():
-    p = _run(["--gpus", "2", "--stub", "--steps", "3", "--warmup", "1", "--frames", "8", "--c5-frames", "16"], _env())
+    p = _run(["--gpus", "2", "--stub", "--full", "--steps", "3", "--warmup", "1", "--frames", "8", "--c5-frames", "16"],
+             _env())
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, p.stdout        # one JSON line, from rank 0 only
@@ -56,11 +57,51 @@ def test_launcher_starts_n_ranks_stub():
 
 
 def test_launcher_single_rank_stub_has_c5():
-    p = _run(["--stub", "--steps", "2", "--warmup", "1", "--frames", "4", "--c5-frames", "8"], _env())
+    p = _run(["--stub", "--full", "--steps", "2", "--warmup", "1", "--frames", "4", "--c5-frames", "8"], _env())
     assert p.returncode == 0, p.stderr[-3000:]
     r = json.loads([ln for ln in p.stdout.splitlines() if ln.startswith("{")][0])
     assert r["n_gpus"] == 1 and "exchange" not in r
     assert r["c5"]["n_ranks"] == 1 and r["c5"]["frames_per_rank"] == 8 and r["c5"]["cross_matches_run"] == 0
+
+
+def test_plain_run_is_headline_only_and_dumps_outputs(tmp_path):
+    """Without --full the line holds the headline and nothing that needs a run of its own; --dump-outputs
+    writes the last timed step's arrays as float .npy files, identical from run to run."""
+    import numpy as np
+    outs = []
+    for name in ("a", "b"):
+        p = _run(["--stub", "--steps", "3", "--warmup", "1", "--frames", "6", "--dump-outputs", str(tmp_path / name)],
+                 _env())
+        assert p.returncode == 0, p.stderr[-3000:]
+        outs.append(p.stdout)
+    lines = [ln for ln in outs[0].splitlines() if ln.startswith("{")]
+    assert len(lines) == 1
+    r = json.loads(lines[0])
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in r
+    assert r["full"] is False and r["steps"] == 3 and r["warmup"] == 1 and r["unit"] == "frames/s"
+    assert r["ms_per_step"] == pytest.approx(1e3 * r["timed_region_s"] / 3)
+    assert r["value"] == pytest.approx(6 * 3 / r["timed_region_s"])
+    for k in ("c5", "c5_n8_per_rank", "localba", "c1", "c2_textured", "c3", "cpu_baseline", "match_roofline", "summary",
+              "latency", "bow", "pose_opt", "stereo", "search_by_projection"):
+        assert k not in r
+    files = sorted(f.name for f in (tmp_path / "a").iterdir())
+    assert files == ["descriptors.npy", "frame_index.npy", "keypoint_counts.npy", "keypoints.npy", "matches.npy"]
+    total = 0
+    for f in files:
+        a, b = np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f)
+        assert a.dtype in (np.float32, np.float64) and np.array_equal(a, b)
+        total += a.nbytes
+    assert total <= 64 << 20
+    # the stub's slots: frame g has (7 g + 3) % 49 keypoints, rows past the count are stored as 0 / -1
+    cnt = np.load(tmp_path / "a" / "keypoint_counts.npy")
+    assert cnt.tolist() == [(7 * g + 3) % 49 for g in range(6)]
+    idx = np.load(tmp_path / "a" / "frame_index.npy").astype(int)
+    d, mt = np.load(tmp_path / "a" / "descriptors.npy"), np.load(tmp_path / "a" / "matches.npy")
+    for j, g in enumerate(idx):
+        n = int(cnt[g])
+        assert d[j, :n, 0].tolist() == [(g * 131 + r * 17) % 251 for r in range(n)]
+        assert not d[j, n:].any() and (mt[:, j, n:] == -1).all()
 
 
 def test_count_gpus_kfd_without_hip(monkeypatch):

@@ -70,27 +70,16 @@ def test_blur_constant_and_impulse(oracle):
     assert np.array_equal(out[7:14, 7:14], ref.astype(np.uint8))
 
 
-def _pattern_from_reference():
-    p = Path("/root/reference/src/ORBextractor.cc")
-    if not p.exists():
-        return None
-    text = p.read_text(errors="replace")
-    start = text.index("bit_pattern_31_[256 * 4]")
-    body = text[text.index("{", start) + 1: text.index("};", start)]
-    body = re.sub(r"/\*.*?\*/", " ", body, flags=re.S)
-    return [int(v) for v in re.findall(r"-?\d+", body)]
-
-
 def test_pattern_table_checksum():
+    """The rBRIEF pattern in csrc/ against the recorded digest of the reference's table: the sha256 of the
+    1024 integers of bit_pattern_31_ (src/ORBextractor.cc) joined with ",", in source order.  The digest is
+    the stored vector, so the test needs nothing outside the repository."""
     inc = (ROOT / "orb_slam2_refactored_amd" / "csrc" / "orb_pattern31.inc").read_text()
     vals = [int(v) for v in re.findall(r"-?\d+", "\n".join(l for l in inc.splitlines() if not l.startswith("//")))]
     assert len(vals) == 1024
     assert min(vals) == -13 and max(vals) == 12
     digest = hashlib.sha256(",".join(map(str, vals)).encode()).hexdigest()
     assert digest == "88df8ca875cc8db56799edd57bb914edad8acb2d48c202b7a464a575b55dbdb8"
-    ref = _pattern_from_reference()
-    if ref is not None:
-        assert ref == vals
 
 
 def test_fast_score_threshold_independent(oracle):

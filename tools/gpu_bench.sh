@@ -8,6 +8,7 @@ if [ -z "$SKIP_TESTS" ]; then
 timeout -k 10 600 python -u -m pytest tests -m gpu -x -q -p no:cacheprovider --timeout 120 --timeout-method thread -ra > gpurun_out/pytest_gpu.log 2>&1 || { tail -30 gpurun_out/pytest_gpu.log; exit 2; }
 tail -2 gpurun_out/pytest_gpu.log
 fi
+BENCH_ARGS="--full $BENCH_ARGS"   # the whole line: rooflines, C5, secondary legs, CPU baselines
 timeout -k 10 600 python -u bench.py $BENCH_ARGS > gpurun_out/bench.log 2>&1 || { tail -30 gpurun_out/bench.log; exit 4; }
 grep '^{' gpurun_out/bench.log | python -c "
 import json,sys

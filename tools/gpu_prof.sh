@@ -6,6 +6,7 @@ export TMPDIR=/tmp
 mkdir -p gpurun_out
 TAG=${1:-r01}
 shift
+set -- --full "$@"   # the legs' kernels are part of the trace
 timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/prof_$TAG -o run -- \
     python3 bench.py --steps 5 --warmup 1 --no-cpu-baseline "$@" > gpurun_out/prof_${TAG}_bench.log 2>&1
 rc=$?

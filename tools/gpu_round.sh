@@ -46,6 +46,7 @@ for step in "$@"; do
     timeout -k 10 300 python tools/diag/desc_determinism.py > gpurun_out/det.log 2>&1 || { tail -20 gpurun_out/det.log; exit 4; }
     tail -3 gpurun_out/det.log ;;
   bench)
+    BENCH_ARGS="--full $BENCH_ARGS"   # the whole line: the summary printed below needs the legs
     timeout -k 10 900 python -u bench.py $BENCH_ARGS > gpurun_out/bench.log 2>&1 || { tail -20 gpurun_out/bench.log; exit 7; }
     grep '^{' gpurun_out/bench.log | python -c "import json,sys; r=json.loads(sys.stdin.read()); print(r['value'], r['ms_per_step']); print(json.dumps(r.get('summary')))" ;;
   ba)

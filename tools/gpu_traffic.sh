@@ -7,7 +7,7 @@ cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 export TMPDIR=/tmp
 TAG=${1:-r02}
 FRAMES=${FRAMES:-8192}
-OUT=gpurun_out/traffic_$TAG
+OUT=${OUT:?set OUT to the folder for logs and profiles}/traffic_$TAG
 mkdir -p $OUT
 for c in FETCH_SIZE WRITE_SIZE; do
   timeout -k 10 300 rocprofv3 --kernel-trace --output-format csv --pmc $c -d $OUT/calib_$c -o run -- \
