@@ -1,4 +1,4 @@
-"""The arithmetic identity behind pyramid_pair_mfma_kernel (orbx.hip), checked on the CPU.
+"""The arithmetic identity behind pyramid_pair_mfma_kernel (orbx_pyramid.h), checked on the CPU.
 
 The horizontal pass of cv::resize INTER_LINEAR 8U (src/ORBextractor.cc:1080-1090 calls it through
 ComputePyramid) is one f16 matrix product per block of 16 output columns: A = the column taps a0 /

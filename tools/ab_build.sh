@@ -1,7 +1,9 @@
 #!/bin/bash
 # Builds an A/B variant of the library: tools/ab/lib_<name>.so = the in-tree objects with <src>.hip
 # recompiled under extra flags.  Usage: tools/ab_build.sh <name> <src (e.g. orbba)> <flags...>
-# With REV=<git revision>, <src>.hip is taken from that revision instead of the working tree.
+# With REV=<git revision>, <src>.hip and the headers it is split into (csrc/<src>_*.h, where that revision
+# has any) are taken from that revision instead of the working tree: they land beside the fetched source,
+# where its quoted includes find them before the in-tree ones.
 # (runs on the CPU side; the .so travels to the GPU box with the tree).
 set -e
 cd "$(dirname "$0")/../orb_slam2_refactored_amd/csrc"
@@ -12,7 +14,15 @@ extra=""
 case $src in orbx|orbm) extra="-mllvm -amdgpu-mfma-vgpr-form";; esac
 [ -n "$NO_VGPR_FORM" ] && extra=""   # MFMA results in AGPRs (the compiler's default form)
 file=$src.hip
-if [ -n "$REV" ]; then file=_build/ab/${src}_$name.hip; git show "$REV:orb_slam2_refactored_amd/csrc/$src.hip" > $file; fi
+if [ -n "$REV" ]; then
+  dir=_build/ab/${src}_$name.rev
+  rm -rf $dir && mkdir -p $dir
+  file=$dir/$src.hip
+  git show "$REV:orb_slam2_refactored_amd/csrc/$src.hip" > $file
+  for h in $(git ls-tree --name-only "$REV" ./ | grep "^${src}_.*\.h$" || true); do
+    git show "$REV:orb_slam2_refactored_amd/csrc/$h" > $dir/$h
+  done
+fi
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -Wall -Wno-unused-result \
     -I../../include -I. $extra "$@" -c $file -o _build/ab/${src}_$name.o
 objs=""

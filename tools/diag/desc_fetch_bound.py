@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Compulsory HBM fetch of describe_kernel per C2 frame (describe fetch <= 12 GB per
-8192-frame launch).  Every kept keypoint reads its level's raw 43x43 neighbourhood (csrc/orbx.hip PATCH:
+8192-frame launch).  Every kept keypoint reads its level's raw 43x43 neighbourhood (csrc/orbx_geom.h PATCH:
 rBRIEF reach 18 + blur 3; ORBextractor.cc:74-140,799-806); the union of those neighbourhoods, in the
 cache lines of the pyramid layout, is what a perfect cache would still fetch once.  Keypoints from the
 oracle's Extract on pan frames (synth.pan_sequence, the bench's C2 workload) and on textured frames.

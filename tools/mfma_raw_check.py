@@ -20,6 +20,8 @@
      DESC_ANGLE_MFMA=0 (the LDS IC_Angle)   1022-1024 differing rows   3 loads at 0 / 5 / 10 wait states
      DESC_ANGLE_FIRST=1                     1018                        1 load at 0 wait states
      shipped, DESC_KEEPALIVE_DIAG, SINCOS_FMA_DIAG       0              none
+   (DESC_ANGLE_FIRST and DESC_KEEPALIVE_DIAG are retired compile-time switches: those builds now live
+   only in the git history, at commit 91c811f.)
    The register allocator reuses a source register of an MFMA it has just issued as the destination
    of the next fragment's LDS load (`v_mfma ... v[16:19] ...` then `ds_read_b128 v[18:21]`); the
    compiler's hazard recognizer inserts nothing, and the outcome depends on whether the load returns

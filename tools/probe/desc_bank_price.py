@@ -1,7 +1,7 @@
 """Price describe's LDS tap-read bank conflicts, and what a per-angle pair placement could save.
 
-Offline model (no GPU): describe's sample stage (orbx.hip describe_kernel, `sample`) reads 7 vertical
-taps of the horizontally blurred patch Hb (u16, row stride HBS) per sample point; lane L of round r
+Offline model (no GPU): describe's sample stage (csrc/orbx_describe.h describe_keypoint, `sample`) reads 7 vertical
+taps of the horizontally blurred patch Hb (u16; row-major with a 40-entry row stride in this model) per sample point; lane L of round r
 samples pair 64 r + L, first point then second point.  A ds_read_u16 is banked as two lane groups of 32
 over 32 dword banks (MI355X_MICROARCH §LDS); identical dwords broadcast; each extra distinct dword on a
 bank adds one cycle.  The 7 taps of one sample sit 20 k dwords apart, a constant bank shift, so every
@@ -13,7 +13,7 @@ It compares, over random keypoint angles:
     balance the banks of both points, found by a greedy swap search at the bucket's centre angle and
     evaluated at random angles inside the bucket (the bits would be restored by one ds_bpermute per
     round);
-  * the column-major blurred map (orbx.hip DESC_HBT=1): the 7 taps as 4 consecutive dwords.
+  * the column-major blurred map (what csrc/orbx_describe.h ships): the 7 taps as 4 consecutive dwords.
 
 usage: python tools/probe/desc_bank_price.py [buckets] [angles]
 """
@@ -97,7 +97,7 @@ def main():
     print(f"  today's placement      {base:.1f}  ({base / ideal:.2f}x)")
     print(f"  {nb}-bucket placement   {opt:.1f}  ({opt / ideal:.2f}x)")
     print(f"  x 7 taps: {7 * base:.0f} -> {7 * opt:.0f} LDS cycles per keypoint")
-    # the column-major map (DESC_HBT): a sample's taps are u16 q .. q + 6 of column 18 + dx, read as
+    # the column-major map (the shipped one): a sample's taps are u16 q .. q + 6 of column 18 + dx, read as
     # dwords q / 2 .. q / 2 + 3 (two ds_read2_b32, each banked as two ds_read_b32)
     hcs = 52
     col = []
