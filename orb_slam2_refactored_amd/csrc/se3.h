@@ -6,7 +6,7 @@
 
 struct Q4 { double x, y, z, w; };
 
-__device__ __forceinline__ Q4 q_from_R(const double* m) {   // Eigen::Quaterniond(Matrix3d)
+__host__ __device__ __forceinline__ Q4 q_from_R(const double* m) {   // Eigen::Quaterniond(Matrix3d)
     Q4 q;
     const double t = m[0] + m[4] + m[8];
     if (t > 0) {
@@ -50,6 +50,15 @@ __device__ __forceinline__ void q_normalize_pos(Q4& q) {   // SE3Quat::normalize
         const double in = 1.0 / n;
         q.x *= in; q.y *= in; q.z *= in; q.w *= in;
     }
+}
+// The host's initial estimates, SE3Quat(R, t) -> Quaterniond(R) normalised (Optimizer.cc:145-150), with
+// Eigen's four divisions.
+inline void quat_from_R(const double* m, double* q4) {
+    Q4 q = q_from_R(m);
+    if (q.w < 0) { q.x = -q.x; q.y = -q.y; q.z = -q.z; q.w = -q.w; }
+    const double n = sqrt(q.x * q.x + q.y * q.y + q.z * q.z + q.w * q.w);
+    if (n > 0) { q.x /= n; q.y /= n; q.z /= n; q.w /= n; }
+    q4[0] = q.x; q4[1] = q.y; q4[2] = q.z; q4[3] = q.w;
 }
 __host__ __device__ __forceinline__ void q_to_R(const double* q4, double* R) {   // toRotationMatrix
     const double x = q4[0], y = q4[1], z = q4[2], w = q4[3];

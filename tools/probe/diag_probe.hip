@@ -1,6 +1,7 @@
-// Probe: ticks of orbba.hip's solve_diag_block (one 16x16 diagonal block of the LocalBA solve) on one
+// Probe: ticks of orbba_solve.h's solve_diag_block (one 16x16 diagonal block of the LocalBA solve) on one
 // wavefront alone, repeated; the rest of the workgroup idle.  Build: see tools/probe/README.
-#include "orbba.hip"
+#include "orbba_dev.h"
+#include "orbba_solve.h"
 #include <cstring>
 using namespace orbamd;
 __global__ __launch_bounds__(64) void diag_probe(unsigned long long* out, int reps) {
