@@ -459,6 +459,77 @@ int orbm_search_by_projection_reloc(const orbm_reloc_batch* b, int32_t* kp_match
 int orbm_search_by_projection_reloc_device(const orbm_reloc_batch* b, int32_t* kp_match, int32_t* n_matches,
                                            void* stream);
 
+/* int ORBmatcher::Fuse(KeyFrame* keyframe, const std::vector<MapPoint*>& mappoints, float th)
+ * (src/ORBmatcher.cc:868-980; LocalMapping::SearchInNeighbors, LocalMapping.cc:606,624, th 3) and
+ * int ORBmatcher::Fuse(KeyFrame* keyframe, const Sim3& Scw, const std::vector<MapPoint*>& mappoints, float th,
+ * std::vector<MapPoint*>& replacePoints) (src/ORBmatcher.cc:982-1088; LoopClosing.cc:648, th 4), batched
+ * over (keyframe, point list) items.  Item i: the keyframe's keypoints [kp_begin[i], kp_begin[i+1])
+ * (keypointsUn pt / octave, uright, descriptorsL rows), its imageBounds, pose and intrinsics; the
+ * candidate points [mp_begin[i], mp_begin[i+1]) in list order.  pose = Rcw then tcw of GetPose(); for
+ * the Sim3 overload Scw.R() and Scw.t() / s (:987).  mp_valid is the caller's skip test, evaluated on
+ * entry over a list of distinct points: mappoint && !isBad() && !IsInKeyFrame(keyframe) (:876), or
+ * !isBad() && !alreadyFound.count(mappoint) (:1002).  mp_xw = GetWorldPos(), mp_max_min = (maxDistance_,
+ * minDistance_) raw (MapPoint.cc:369-377), mp_normal = GetNormal(), mp_desc = GetDescriptor().
+ * On the device, in the reference's order and float expressions: Xc = Rcw * Xw + tcw, Xc.z < 0 rejects
+ * (:883), CameraToImage and imageBounds.Contains (:886-892), ur = u - bf / Xc.z (:894), the
+ * distance-invariance gate with 0.8f / 1.2f (:896-903, MapPoint.cc:382-392), the viewing-angle gate
+ * PO.dot(Pn) < 0.5 * dist3D (:905-908), PredictScale (MapPoint.cc:394-403, ::log(double)), the window
+ * GetFeaturesInArea(u, v, th * scaleFactors[predictedScale]) (:913-915), the levels [predictedScale - 1,
+ * predictedScale] (:930), with chi2_gate the reprojection gates 7.8 (uright >= 0) / 5.99 on
+ * NormSq * invSigmaSq[octave] (:933-945; the Sim3 overload has none), and the first minimum descriptor
+ * distance in scan order (:947-953).  Keypoints holding a map point are not skipped, and the per-point
+ * result does not depend on the Replace / AddObservation calls of earlier iterations, so the caller
+ * applies :957-976 (or :1070-1084) in list order from best_idx. */
+typedef struct orbm_fuse_batch {
+    int32_t        n_items, total_kp, total_mp;
+    const int32_t* kp_begin;     /* n_items + 1 */
+    const float*   kp_xy;        /* keyframe keypointsUn pt, total_kp x 2 */
+    const int32_t* kp_octave;
+    const float*   kp_uright;    /* uright (-1: monocular keypoint); read with chi2_gate only */
+    const uint8_t* kp_desc;      /* total_kp x 32 */
+    const float*   bounds;       /* n_items x 4: imageBounds minx, maxx, miny, maxy */
+    const float*   pose;         /* n_items x 12: Rcw (row-major 3x3) then tcw */
+    const float*   camera;       /* n_items x 5: fx, fy, cx, cy, bf */
+    const int32_t* mp_begin;     /* n_items + 1 */
+    const uint8_t* mp_valid;
+    const float*   mp_xw;        /* total_mp x 3 */
+    const float*   mp_max_min;   /* total_mp x 2: maxDistance_, minDistance_ */
+    const float*   mp_normal;    /* total_mp x 3 */
+    const uint8_t* mp_desc;      /* total_mp x 32 */
+    int32_t        n_levels;
+    const float*   scale_factors;/* host, n_levels (keyframe->pyramid.scaleFactors) */
+    const float*   inv_sigma2;   /* host, n_levels (pyramid.invSigmaSq); read with chi2_gate only */
+    float          log_scale_factor; /* pyramid.logScaleFactor */
+    float          th;
+    int32_t        chi2_gate;    /* 1: the first overload (:933-945); 0: the Sim3 overload */
+} orbm_fuse_batch;
+
+/* best_idx[m]: keyframe-relative bestIdx of point m when bestDist <= TH_LOW (50), else -1.
+ * best_dist[m]: the minimum distance found, 256 when no candidate passed the gates.  n_fused[i]: Fuse's
+ * return value (nfused++ runs on both branches of :957-976), the count of best_idx >= 0; -1 (device
+ * entry, with every best_idx of the item -1) when the keyframe has more than ORBM_PROJ_MAX_KP keypoints.
+ * Host entry: every pointer is host memory, synchronous, offsets validated. */
+int orbm_fuse(const orbm_fuse_batch* b, int32_t* best_idx, int32_t* best_dist, int32_t* n_fused, int device);
+/* Device entry: every array in HBM except scale_factors / inv_sigma2; enqueue only on `stream`. */
+int orbm_fuse_device(const orbm_fuse_batch* b, int32_t* best_idx, int32_t* best_dist, int32_t* n_fused, void* stream);
+
+/* int ORBmatcher::SearchByProjection(const KeyFrame* keyframe, const Sim3& Scw, const std::vector<MapPoint*>&
+ * mappoints, std::vector<MapPoint*>& matched, int th) (src/ORBmatcher.cc:518-612; LoopClosing::ComputeSim3,
+ * LoopClosing.cc:277, th 10) on an orbm_fuse_batch (pose = Scw.R(), Scw.t() / s (:523); mp_valid =
+ * !isBad() && !alreadyFound.count(mappoint) (:537); kp_uright, inv_sigma2, chi2_gate and the camera's bf
+ * are not read) plus kp_claimed[k] = matched[k] != NULL on entry (total_kp, NULL: none).  The same
+ * projection and gates (:540-572), then for each point in list order the first minimum distance over
+ * the window's keypoints of levels [predictedScale - 1, predictedScale] that hold no match yet (:588),
+ * bestDist <= TH_LOW, and the claim matched[bestIdx] = mappoint (:604-608).  kp_match[k] = item-relative
+ * index of the point the call assigned to keypoint k, -1 when none; n_matches[i] = the return value (-1,
+ * device entry, when the keyframe has more than ORBM_PROJ_MAX_KP keypoints).
+ * Host entry: every pointer is host memory, synchronous, offsets validated. */
+int orbm_search_by_projection_sim3(const orbm_fuse_batch* b, const uint8_t* kp_claimed, int32_t* kp_match,
+                                   int32_t* n_matches, int device);
+/* Device entry: every array in HBM except scale_factors; enqueue only on `stream`. */
+int orbm_search_by_projection_sim3_device(const orbm_fuse_batch* b, const uint8_t* kp_claimed, int32_t* kp_match,
+                                          int32_t* n_matches, void* stream);
+
 /* int ORBmatcher::SearchForInitialization(Frame& F1, Frame& F2, std::vector<cv::Point2f>& vbPrevMatched,
  * std::vector<int>& vnMatches12, int windowSize) (include/ORBmatcher.h:81, src/ORBmatcher.cc:614-694;
  * Tracking::MonocularInitialization, Tracking.cc:1052), batched over initialisation pairs.

@@ -412,6 +412,39 @@ inline int SearchByProjectionReloc(const orbm_reloc_batch& b, std::vector<int32_
     return nm;
 }
 
+// int ORBmatcher::Fuse(KeyFrame*, const std::vector<MapPoint*>&, float th) (src/ORBmatcher.cc:868-980,
+// chi2_gate = 1) and Fuse(KeyFrame*, const Sim3& Scw, points, th, replacePoints) (:982-1088, chi2_gate = 0,
+// pose = Scw.R(), Scw.t() / s), batched over (keyframe, point list) items on HBM arrays (orbm_fuse_batch:
+// the caller marks mp_valid = mappoint && !isBad() && !IsInKeyFrame(keyframe), or !alreadyFound.count(
+// mappoint), on entry over distinct points).  Enqueue only; best_idx[m] = bestIdx when bestDist <= TH_LOW,
+// else -1.  The caller then walks the list in order and applies Replace / AddObservation / AddMapPoint
+// (:957-976) or replacePoints[i] (:1070-1084) from best_idx.
+inline void FuseBatch(const orbm_fuse_batch& b, int32_t* d_best_idx, int32_t* d_best_dist, int32_t* d_n_fused,
+                      void* stream = nullptr) {
+    check(orbm_fuse_device(&b, d_best_idx, d_best_dist, d_n_fused, stream), "orbm_fuse_device");
+}
+// The same for one keyframe on host arrays; returns nfused.
+inline int Fuse(const orbm_fuse_batch& b, std::vector<int32_t>& bestIdx, std::vector<int32_t>& bestDist, int device = 0) {
+    if (b.n_items != 1) throw std::invalid_argument("Fuse: one keyframe per call (use the batch form)");
+    bestIdx.assign(std::max(b.total_mp, 1), -1);
+    bestDist.assign(std::max(b.total_mp, 1), 256);
+    int32_t nf = 0;
+    check(orbm_fuse(&b, bestIdx.data(), bestDist.data(), &nf, device), "orbm_fuse");
+    bestIdx.resize(b.total_mp);
+    bestDist.resize(b.total_mp);
+    return nf;
+}
+
+// int ORBmatcher::SearchByProjection(const KeyFrame*, const Sim3& Scw, const std::vector<MapPoint*>&,
+// std::vector<MapPoint*>& matched, int th) (src/ORBmatcher.cc:518-612), batched on HBM arrays: the
+// orbm_fuse_batch plus d_kp_claimed[k] = matched[k] != nullptr on entry (nullptr: none).  Enqueue only;
+// kp_match[k] = item-relative index of the point assigned to keypoint k (matched[k] = mappoints[idx]) or -1.
+inline void SearchByProjectionSim3Batch(const orbm_fuse_batch& b, const uint8_t* d_kp_claimed, int32_t* d_kp_match,
+                                        int32_t* d_n_matches, void* stream = nullptr) {
+    check(orbm_search_by_projection_sim3_device(&b, d_kp_claimed, d_kp_match, d_n_matches, stream),
+          "orbm_search_by_projection_sim3_device");
+}
+
 // DBoW2 ORBVocabulary: loadFromTextFile + transform(features, BowVector&, FeatureVector&, levelsup)
 // (TemplatedVocabulary.h:1130-1196, :1341-1431) with the reference's container types.
 class ORBVocabulary {

@@ -8,8 +8,11 @@ Host mirrors of the reference's interfaces (tiantianxuabc/ORB_SLAM2_Refactored):
 All compute runs in liborbslam2_amd.so (HIP kernels behind include/orbslam2_amd.h).
 """
 from .extractor import ORBextractor, KP_DTYPE
-from .matcher import ORBmatcher, ComputeStereoMatches
+from .matcher import (ORBmatcher, ComputeStereoMatches, Fuse, fuse_device, SearchByProjectionSim3,
+                      search_by_projection_sim3_device)
 from . import optimizer
 from .synth import synth_image, shifted_pair, stereo_pair, make_pose_batch
 
-__all__ = ["ORBextractor", "ORBmatcher", "ComputeStereoMatches", "optimizer", "KP_DTYPE", "synth_image", "shifted_pair", "stereo_pair", "make_pose_batch"]
+__all__ = ["ORBextractor", "ORBmatcher", "ComputeStereoMatches", "Fuse", "fuse_device", "SearchByProjectionSim3",
+           "search_by_projection_sim3_device", "optimizer", "KP_DTYPE", "synth_image", "shifted_pair", "stereo_pair",
+           "make_pose_batch"]

@@ -21,6 +21,8 @@
 //                    when fewer than two of the K are unclaimed and more candidates exist, the
 //                    wavefront rescans that map point's window against the bitmap.  Then the
 //                    TH_HIGH / same-level ratio test and the claim.
+// The other projection searches below share the grid: the motion-model and relocalisation forms
+// (pjm_*), SearchForInitialization (pi_*), and Fuse / the Sim3 search (orbp_fuse.h).
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -439,6 +441,8 @@ struct PjmExtra {
     const float* mp_angle;
     int32_t* choice;   // total_mp: accepted idx2 or -1
     int max_dist;      // TH_HIGH (:1347); ORBdist for SearchByProjection(Frame&, KeyFrame*, ...) (:1425)
+    int lvl_up;        // upper end of the level window when motion == 0: [octave - 1, octave + lvl_up].
+                       // 1 for the motion and relocalisation entries, 0 for the Sim3 search (:592)
 };
 
 // The window scan of one last-frame point (GetFeaturesInArea + the gates of :1329-1339): each lane's
@@ -457,7 +461,7 @@ __device__ __forceinline__ uint32_t pjm_scan(const PjArgs& a, const PjmExtra& e,
     const float r = a.th * a.scale[oct];   // :1316
     // :1318-1319 through GetFeaturesInArea's checkLevels (maxLevel < 0 -> nlevels)
     const int lo = mot == 1 ? oct : (mot == 2 ? 0 : oct - 1);
-    const int hi = mot == 1 ? a.n_levels : (mot == 2 ? oct : oct + 1);
+    const int hi = mot == 1 ? a.n_levels : (mot == 2 ? oct : oct + e.lvl_up);
     const float u = a.mp_proj[3 * (size_t)j], v = a.mp_proj[3 * (size_t)j + 1];
     const float uR = a.kp_ur ? a.mp_proj[3 * (size_t)j + 2] : 0.f;
     const int mincx = max((int)floorf(invW * (u - r - minx)), 0);
@@ -1017,10 +1021,13 @@ static int reloc_common(const orbm_reloc_batch* b, PjArgs& a, RelocExtra& r, Pjm
     a.total_mp = b->total_mp;
     r.log_sf = b->log_scale_factor;
     e.max_dist = b->orb_dist;
+    e.lvl_up = 1;
     return ORB_OK;
 }
 
 }  // namespace orbamd
+
+#include "orbp_fuse.h"
 
 using namespace orbamd;
 
@@ -1157,7 +1164,7 @@ extern "C" int orbm_search_by_projection_motion_device(const orbm_motion_batch* 
     const size_t base = pj_workspace_bytes(b->n_frames, b->total_kp, b->total_mp);
     if ((rc = g_pj.ws.reserve(base + align_up((size_t)std::max(b->total_mp, 1) * 4, 256)))) return rc;
     pj_carve(a, g_pj.ws.as<char>(), b->n_frames, b->total_kp, b->total_mp);
-    PjmExtra e{b->motion, b->kp_angle, b->mp_angle, reinterpret_cast<int32_t*>(g_pj.ws.as<char>() + base), PJ_TH_HIGH};
+    PjmExtra e{b->motion, b->kp_angle, b->mp_angle, reinterpret_cast<int32_t*>(g_pj.ws.as<char>() + base), PJ_TH_HIGH, 1};
     hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL(pj_grid_kernel, dim3(a.n_frames), dim3(256), 0, st, a);
     ORB_HIP_TRY(hipGetLastError());
@@ -1372,5 +1379,118 @@ extern "C" int orbm_search_by_projection_reloc(const orbm_reloc_batch* b, int32_
     if ((rc = launch_reloc(a, r, e, g_pj.ws.as<char>(), K, b->check_orientation, nullptr))) return rc;
     if (K) ORB_HIP_TRY(hipMemcpy(kp_match, d + o_km, (size_t)K * 4, hipMemcpyDeviceToHost));
     ORB_HIP_TRY(hipMemcpy(n_matches, d + o_nm, (size_t)F * 4, hipMemcpyDeviceToHost));
+    return ORB_OK;
+}
+
+
+extern "C" int orbm_fuse_device(const orbm_fuse_batch* b, int32_t* best_idx, int32_t* best_dist, int32_t* n_fused,
+                                void* stream) {
+    PjArgs a;
+    FuseExtra r;
+    PjmExtra e;
+    int rc;
+    if ((rc = fuse_common(b, false, a, r, e))) return rc;
+    if (b->n_items == 0) return ORB_OK;
+    ORB_CHECK_ARG(n_fused && (b->total_mp == 0 || (best_idx && best_dist)), "null output array");
+    a.kp_begin = b->kp_begin; a.kp_xy = b->kp_xy; a.kp_oct = b->kp_octave; a.kp_ur = b->kp_uright;
+    a.kp_desc = b->kp_desc; a.bounds = b->bounds; a.mp_begin = b->mp_begin; a.mp_desc = b->mp_desc;
+    r.pose = b->pose; r.camera = b->camera; r.valid = b->mp_valid; r.xw = b->mp_xw; r.max_min = b->mp_max_min;
+    r.normal = b->mp_normal; r.best_idx = best_idx; r.best_dist = best_dist; r.n_fused = n_fused;
+    int dev = 0;
+    ORB_HIP_TRY(hipGetDevice(&dev));
+    if (g_pj.device != dev) {
+        g_pj.ws.release();
+        g_pj.io.release();
+        g_pj.device = dev;
+    }
+    if ((rc = g_pj.ws.reserve(fuse_workspace_bytes(b->n_items, b->total_kp, b->total_mp)))) return rc;
+    fuse_carve(a, r, e, g_pj.ws.as<char>(), b->total_kp);
+    return launch_fuse(a, r, (hipStream_t)stream);
+}
+
+extern "C" int orbm_fuse(const orbm_fuse_batch* b, int32_t* best_idx, int32_t* best_dist, int32_t* n_fused, int device) {
+    PjArgs a;
+    FuseExtra r;
+    PjmExtra e;
+    int rc;
+    if ((rc = fuse_common(b, false, a, r, e))) return rc;   // the checks, before any copy
+    const int F = b->n_items, M = b->total_mp;
+    if (F == 0) return ORB_OK;
+    ORB_CHECK_ARG(n_fused && (M == 0 || (best_idx && best_dist)), "null output array");
+    if ((rc = fuse_check_offsets(b))) return rc;
+    ORB_HIP_TRY(hipSetDevice(device));
+    if (g_pj.device != device) {
+        g_pj.ws.release();
+        g_pj.io.release();
+        g_pj.device = device;
+    }
+    const size_t o_bd = align_up((size_t)std::max(M, 1) * 4, 256), o_nf = 2 * o_bd;
+    orbm_fuse_batch d;
+    const uint8_t* d_claimed;
+    char* out;
+    if ((rc = fuse_upload(b, nullptr, g_pj.io, o_nf + (size_t)F * 4, d, d_claimed, out))) return rc;
+    if ((rc = orbm_fuse_device(&d, (int32_t*)out, (int32_t*)(out + o_bd), (int32_t*)(out + o_nf), nullptr))) return rc;
+    if (M) {
+        ORB_HIP_TRY(hipMemcpy(best_idx, out, (size_t)M * 4, hipMemcpyDeviceToHost));
+        ORB_HIP_TRY(hipMemcpy(best_dist, out + o_bd, (size_t)M * 4, hipMemcpyDeviceToHost));
+    }
+    ORB_HIP_TRY(hipMemcpy(n_fused, out + o_nf, (size_t)F * 4, hipMemcpyDeviceToHost));
+    return ORB_OK;
+}
+
+extern "C" int orbm_search_by_projection_sim3_device(const orbm_fuse_batch* b, const uint8_t* kp_claimed,
+                                                     int32_t* kp_match, int32_t* n_matches, void* stream) {
+    PjArgs a;
+    FuseExtra r;
+    PjmExtra e;
+    int rc;
+    if ((rc = fuse_common(b, true, a, r, e))) return rc;
+    if (b->n_items == 0) return ORB_OK;
+    ORB_CHECK_ARG(n_matches && (b->total_kp == 0 || kp_match), "null output array");
+    a.kp_begin = b->kp_begin; a.kp_xy = b->kp_xy; a.kp_oct = b->kp_octave; a.kp_ur = nullptr;   // no stereo gate
+    a.kp_desc = b->kp_desc; a.kp_claimed = kp_claimed; a.bounds = b->bounds;
+    a.mp_begin = b->mp_begin; a.mp_desc = b->mp_desc; a.mp_has_obs = nullptr;   // every accepted point claims (:606)
+    a.kp_match = kp_match;
+    a.n_matches = n_matches;
+    r.pose = b->pose; r.camera = b->camera; r.valid = b->mp_valid; r.xw = b->mp_xw; r.max_min = b->mp_max_min;
+    r.normal = b->mp_normal;
+    int dev = 0;
+    ORB_HIP_TRY(hipGetDevice(&dev));
+    if (g_pj.device != dev) {
+        g_pj.ws.release();
+        g_pj.io.release();
+        g_pj.device = dev;
+    }
+    if ((rc = g_pj.ws.reserve(fuse_workspace_bytes(b->n_items, b->total_kp, b->total_mp)))) return rc;
+    fuse_carve(a, r, e, g_pj.ws.as<char>(), b->total_kp);
+    return launch_sim3(a, r, e, (hipStream_t)stream);
+}
+
+extern "C" int orbm_search_by_projection_sim3(const orbm_fuse_batch* b, const uint8_t* kp_claimed, int32_t* kp_match,
+                                              int32_t* n_matches, int device) {
+    PjArgs a;
+    FuseExtra r;
+    PjmExtra e;
+    int rc;
+    if ((rc = fuse_common(b, true, a, r, e))) return rc;   // the checks, before any copy
+    const int F = b->n_items, K = b->total_kp;
+    if (F == 0) return ORB_OK;
+    ORB_CHECK_ARG(n_matches && (K == 0 || kp_match), "null output array");
+    if ((rc = fuse_check_offsets(b))) return rc;
+    ORB_HIP_TRY(hipSetDevice(device));
+    if (g_pj.device != device) {
+        g_pj.ws.release();
+        g_pj.io.release();
+        g_pj.device = device;
+    }
+    const size_t o_nm = align_up((size_t)std::max(K, 1) * 4, 256);
+    orbm_fuse_batch d;
+    const uint8_t* d_claimed;
+    char* out;
+    if ((rc = fuse_upload(b, kp_claimed, g_pj.io, o_nm + (size_t)F * 4, d, d_claimed, out))) return rc;
+    if ((rc = orbm_search_by_projection_sim3_device(&d, d_claimed, (int32_t*)out, (int32_t*)(out + o_nm), nullptr)))
+        return rc;
+    if (K) ORB_HIP_TRY(hipMemcpy(kp_match, out, (size_t)K * 4, hipMemcpyDeviceToHost));
+    ORB_HIP_TRY(hipMemcpy(n_matches, out + o_nm, (size_t)F * 4, hipMemcpyDeviceToHost));
     return ORB_OK;
 }

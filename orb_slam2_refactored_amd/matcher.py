@@ -407,12 +407,12 @@ _BATCH_ROWS = {
 }
 
 
-def _check_batch_rows(batch: dict, keys, dims: dict, what: str):
+def _check_batch_rows(batch: dict, keys, dims: dict, what: str, rows: dict = _BATCH_ROWS):
     for k in keys:
         a = batch.get(k)
         if a is None:
             continue
-        sym, per = _BATCH_ROWS[k]
+        sym, per = rows[k]
         want = dims[sym] * per
         n = int(a.numel()) if hasattr(a, "numel") else int(np.size(a))
         if n < want:
@@ -563,4 +563,130 @@ def search_by_projection_reloc_device(batch: dict, kp_match=None, n_matches=None
     check(lib().orbm_search_by_projection_reloc_device(C.byref(rb), tptr(kp_match), tptr(n_matches),
                                                        stream_ptr(stream)),
           "orbm_search_by_projection_reloc_device")
+    return kp_match, n_matches
+
+
+_FUSE_KEYS = (("kp_begin", np.int32), ("kp_xy", np.float32), ("kp_octave", np.int32), ("kp_uright", np.float32),
+              ("kp_desc", np.uint8), ("bounds", np.float32), ("pose", np.float32), ("camera", np.float32),
+              ("mp_begin", np.int32), ("mp_valid", np.uint8), ("mp_xw", np.float32), ("mp_max_min", np.float32),
+              ("mp_normal", np.float32), ("mp_desc", np.uint8))
+_FUSE_ROWS = dict(_BATCH_ROWS, camera=("F", 5), mp_normal=("M", 3))   # fx, fy, cx, cy, bf
+
+
+def _fuse_check(batch, dims, chi2, claimed, what):
+    """Every orbm_fuse_batch array present (kp_uright only with the chi2 gate) and long enough."""
+    for k, _ in _FUSE_KEYS:
+        if batch.get(k) is None and (k != "kp_uright" or chi2):
+            raise ValueError(f"{what}: {k} is required")
+    if chi2 and batch.get("inv_sigma2") is None:
+        raise ValueError(f"{what}: inv_sigma2 is required with chi2_gate")
+    keys = [k for k, _ in _FUSE_KEYS] + (["kp_claimed"] if claimed else [])
+    _check_batch_rows(batch, keys, dims, what, _FUSE_ROWS)
+
+
+def _fuse_struct(batch, conv, K, M, chi2):
+    from ._lib import FuseBatch
+    sf = np.ascontiguousarray(batch["scale_factors"], np.float32)
+    s2 = np.ascontiguousarray(batch["inv_sigma2"], np.float32) if batch.get("inv_sigma2") is not None else None
+    if s2 is not None and len(s2) < len(sf):
+        raise ValueError("inv_sigma2 must have one entry per pyramid level")
+    F = len(batch["kp_begin"]) - 1
+    fb = FuseBatch(F, K, M, *[conv(batch[k], dt) if batch.get(k) is not None else None for k, dt in _FUSE_KEYS],
+                   len(sf), ptr(sf), ptr(s2) if s2 is not None else None, float(batch["log_scale_factor"]),
+                   float(batch["th"]), int(bool(chi2)))
+    return fb, (sf, s2)
+
+
+def _host_conv(keep):
+    def conv(a, dt):
+        a = np.ascontiguousarray(a, dt)
+        keep.append(a)
+        return ptr(a)
+    return conv
+
+
+def Fuse(batch: dict, device: int = 0):
+    """ORBmatcher::Fuse(KeyFrame*, const std::vector<MapPoint*>&, th) (src/ORBmatcher.cc:868-980, chi2_gate
+    true) and Fuse(KeyFrame*, const Sim3&, points, th, replacePoints) (:982-1088, chi2_gate false), batched
+    over (keyframe, point list) items on host arrays (orbm_fuse_batch fields).  Returns (best_idx
+    [total_mp] = keyframe-relative bestIdx when bestDist <= TH_LOW else -1, best_dist [total_mp] (256:
+    no candidate), n_fused [n_items] = the return value).  The caller applies Replace / AddObservation in
+    list order from best_idx."""
+    F = len(batch["kp_begin"]) - 1
+    K, M = int(batch["kp_begin"][-1]), int(batch["mp_begin"][-1])
+    chi2 = bool(batch["chi2_gate"])
+    _fuse_check(batch, {"F": F, "F1": F + 1, "K": K, "M": M}, chi2, False, "Fuse")
+    keep = []
+    fb, _host = _fuse_struct(batch, _host_conv(keep), K, M, chi2)
+    bi = np.empty(max(M, 1), np.int32)
+    bd = np.empty(max(M, 1), np.int32)
+    nf = np.empty(max(F, 1), np.int32)
+    check(lib().orbm_fuse(C.byref(fb), ptr(bi), ptr(bd), ptr(nf), int(device)), "orbm_fuse")
+    return bi[:M], bd[:M], nf[:F]
+
+
+def fuse_device(batch: dict, best_idx=None, best_dist=None, n_fused=None, stream=None):
+    """Device form of Fuse: GPU tensors for the orbm_fuse_batch arrays, host values for scale_factors,
+    inv_sigma2, log_scale_factor, th and chi2_gate.  n_fused[i] = -1 (and every best_idx of the item -1)
+    when a keyframe has more than ORBM_PROJ_MAX_KP keypoints."""
+    import torch
+    kb = batch["kp_begin"]
+    F = kb.numel() - 1
+    chi2 = bool(batch["chi2_gate"])
+    _check_device_dtypes(batch, _FUSE_KEYS, "fuse_device")
+    K = int(batch["kp_xy"].shape[0]) if batch.get("kp_xy") is not None else 0
+    M = int(batch["mp_xw"].shape[0]) if batch.get("mp_xw") is not None else 0
+    _fuse_check(batch, {"F": F, "F1": F + 1, "K": K, "M": M}, chi2, False, "fuse_device")
+    if best_idx is None:
+        best_idx = torch.empty(max(M, 1), dtype=torch.int32, device=kb.device)
+    if best_dist is None:
+        best_dist = torch.empty(max(M, 1), dtype=torch.int32, device=kb.device)
+    if n_fused is None:
+        n_fused = torch.empty(max(F, 1), dtype=torch.int32, device=kb.device)
+    fb, _host = _fuse_struct(batch, lambda t, dt: tptr(t), K, M, chi2)
+    check(lib().orbm_fuse_device(C.byref(fb), tptr(best_idx), tptr(best_dist), tptr(n_fused), stream_ptr(stream)),
+          "orbm_fuse_device")
+    return best_idx, best_dist, n_fused
+
+
+def SearchByProjectionSim3(batch: dict, device: int = 0):
+    """ORBmatcher::SearchByProjection(const KeyFrame*, const Sim3& Scw, points, matched, th)
+    (src/ORBmatcher.cc:518-612, LoopClosing::ComputeSim3) batched over (keyframe, point list) items on host
+    arrays: the orbm_fuse_batch fields (kp_uright / inv_sigma2 / chi2_gate unused) plus kp_claimed =
+    matched[k] != nullptr on entry (may be None).  Returns (kp_match [total_kp] = item-relative point
+    index assigned to each keypoint or -1, n_matches [n_items])."""
+    F = len(batch["kp_begin"]) - 1
+    K, M = int(batch["kp_begin"][-1]), int(batch["mp_begin"][-1])
+    claimed = batch.get("kp_claimed")
+    _fuse_check(batch, {"F": F, "F1": F + 1, "K": K, "M": M}, False, claimed is not None, "SearchByProjectionSim3")
+    keep = []
+    conv = _host_conv(keep)
+    fb, _host = _fuse_struct(batch, conv, K, M, False)
+    km = np.empty(max(K, 1), np.int32)
+    nm = np.empty(max(F, 1), np.int32)
+    check(lib().orbm_search_by_projection_sim3(C.byref(fb), conv(claimed, np.uint8) if claimed is not None else None,
+                                               ptr(km), ptr(nm), int(device)), "orbm_search_by_projection_sim3")
+    return km[:K], nm[:F]
+
+
+def search_by_projection_sim3_device(batch: dict, kp_match=None, n_matches=None, stream=None):
+    """Device form of SearchByProjectionSim3: GPU tensors for the arrays (kp_claimed may be None), host
+    values for scale_factors, log_scale_factor and th."""
+    import torch
+    kb = batch["kp_begin"]
+    F = kb.numel() - 1
+    claimed = batch.get("kp_claimed")
+    _check_device_dtypes(batch, _FUSE_KEYS + (("kp_claimed", np.uint8),), "search_by_projection_sim3_device")
+    K = int(batch["kp_xy"].shape[0]) if batch.get("kp_xy") is not None else 0
+    M = int(batch["mp_xw"].shape[0]) if batch.get("mp_xw") is not None else 0
+    _fuse_check(batch, {"F": F, "F1": F + 1, "K": K, "M": M}, False, claimed is not None,
+                "search_by_projection_sim3_device")
+    if kp_match is None:
+        kp_match = torch.empty(max(K, 1), dtype=torch.int32, device=kb.device)
+    if n_matches is None:
+        n_matches = torch.empty(max(F, 1), dtype=torch.int32, device=kb.device)
+    fb, _host = _fuse_struct(batch, lambda t, dt: tptr(t), K, M, False)
+    check(lib().orbm_search_by_projection_sim3_device(C.byref(fb), tptr(claimed) if claimed is not None else None,
+                                                      tptr(kp_match), tptr(n_matches), stream_ptr(stream)),
+          "orbm_search_by_projection_sim3_device")
     return kp_match, n_matches

@@ -666,3 +666,148 @@ def make_reloc_batch(seed: int = 0, n_frames: int = 4, n_kp=2000, n_mp=600, th: 
     out.update(scale_factors=cum, log_scale_factor=float(np.float32(np.log(np.float64(np.float32(1.2))))), th=float(th),
                orb_dist=int(orb_dist), check_orientation=bool(check_orientation))
     return out
+
+
+def make_fuse_batch(seed: int = 0, n_items: int = 4, n_kp=2000, n_mp=1500, th: float = 3.0, chi2_gate: bool = True,
+                    dup_frac: float = 0.0, claimed_frac: float = 0.0):
+    """ORBmatcher::Fuse / Sim3 SearchByProjection inputs (orbm_fuse_batch, host arrays, plus kp_claimed for
+    the Sim3 search) shaped like LocalMapping::SearchInNeighbors (LocalMapping.cc:606,624: th 3) and
+    LoopClosing (th 4 / 10) on the KITTI stereo camera.  Per item a keyframe pose (small rotation, a few
+    metres of translation) and n_mp candidate points (90 % valid):
+      2 % behind the camera, ~4 % projecting outside the image, 2.5 % outside the invariance range
+      (maxDistance_ = dist / 2 or dist * 6; else dist * 1.2^o * U(0.9, 1.1), minDistance_ = max / 1.2^7),
+      normals 0-50 deg off the viewing ray (94 %), 65-120 deg (3 %) or around the 60 deg gate (3 %);
+      ~70 % observed by a keypoint near the projection: octave = predicted scale + {-1, 0, 0, 1, 3}, 0-70
+      flipped bits (92 % up to 45, the rest above: some best distances exceed TH_LOW), pixel noise
+      N(0, s * 1.2^octave) with s = 0.8 (92 %) or 2.5 so the chi2 gates pass and fail at every octave,
+      half stereo (uright near u - bf / z, also noisy) and half uright = -1; 3 % of the stereo ones have
+      uright = 0 exactly (still stereo: the gate is uright >= 0);
+      8 % of the observed points get a second keypoint with the identical descriptor in another grid cell
+      of the window, the one earlier in scan order holding the higher index (a tie index order would
+      decide the other way);
+      `dup_frac` of the points copy an earlier observed point (position, a descriptor 0-10 bits away) and
+      compete for its keypoint (the Sim3 search's claims).
+    The other keypoints are random (half stereo); `claimed_frac` of all keypoints hold a match on entry.
+    n_kp / n_mp: int or per-item list."""
+    rng = np.random.default_rng(seed)
+    kps = [int(n_kp)] * n_items if np.isscalar(n_kp) else [int(v) for v in n_kp]
+    mps = [int(n_mp)] * n_items if np.isscalar(n_mp) else [int(v) for v in n_mp]
+    fx, fy, cx, cy = np.float32(KITTI["fx"]), np.float32(KITTI["fy"]), np.float32(KITTI["cx"]), np.float32(KITTI["cy"])
+    bf = np.float32(KITTI["bf"])
+    W, H = np.float32(KITTI["width"]), np.float32(KITTI["height"])
+    cum = np.ones(8, np.float32)
+    for i in range(1, 8):
+        cum[i] = np.float32(cum[i - 1] * np.float32(1.2))
+    invW, invH = np.float32(64) / W, np.float32(48) / H
+
+    def cell(px, py):   # FeaturesGrid::AssignFeatures' cell of a keypoint
+        return (int(np.round(float(invW * np.float32(px)))), int(np.round(float(invH * np.float32(py)))))
+
+    def flip(d, nbits):
+        d = d.copy()
+        for bit in rng.choice(256, size=nbits, replace=False):
+            d[bit >> 3] ^= np.uint8(1 << (bit & 7))
+        return d
+
+    F = dict(kp_xy=[], kp_octave=[], kp_uright=[], kp_desc=[], kp_claimed=[], bounds=[], pose=[], camera=[],
+             mp_valid=[], mp_xw=[], mp_max_min=[], mp_normal=[], mp_desc=[])
+    for f in range(n_items):
+        n, m = kps[f], mps[f]
+        Rcw = _small_rot(rng, 3.0).astype(np.float32)
+        tcw = rng.normal(0, 2.0, 3).astype(np.float32)
+        z = rng.uniform(4, 40, m)
+        z = np.where(rng.random(m) < 0.02, -rng.uniform(2, 30, m), z)
+        u = rng.uniform(-10, float(W) + 10, m)
+        v = rng.uniform(-4, float(H) + 4, m)
+        o = rng.integers(0, 8, m)
+        mscale = (1.2 ** o) * rng.uniform(0.9, 1.1, m)
+        mscale = np.where(rng.random(m) < 0.025, rng.choice([0.5, 6.0], m), mscale)
+        mdesc = rng.integers(0, 256, size=(m, 32), dtype=np.uint8)
+        observed = rng.random(m) < 0.72
+        src = np.full(m, -1)
+        for j in range(1, m):   # copies of an earlier observed point
+            if rng.random() < dup_frac:
+                cand = np.nonzero(observed[:j] & (src[:j] < 0))[0]
+                if len(cand):
+                    j0 = int(rng.choice(cand))
+                    src[j], observed[j] = j0, False
+                    z[j], u[j], v[j], mscale[j] = z[j0], u[j0] + rng.normal(0, 0.3), v[j0] + rng.normal(0, 0.3), mscale[j0]
+                    mdesc[j] = flip(mdesc[j0], int(rng.integers(0, 11)))
+        Xc = np.stack([(u - cx) * z / fx, (v - cy) * z / fy, z], 1)
+        Xw = ((Xc - tcw[None]) @ Rcw).astype(np.float32)   # Xw = Rcw^T (Xc - tcw)
+        Ow = -(Rcw.T @ tcw)
+        PO = Xw - Ow[None]
+        dist = np.linalg.norm(PO, axis=1)
+        maxd = dist * mscale
+        mind = maxd / cum[7]
+        # normals: the viewing ray turned by ang about a random axis perpendicular to it
+        ray = PO / np.maximum(dist, 1e-9)[:, None]
+        kind = rng.random(m)
+        ang = np.deg2rad(np.where(kind < 0.94, rng.uniform(0, 50, m),
+                                  np.where(kind < 0.97, rng.uniform(65, 120, m), rng.uniform(58, 62, m))))
+        perp = np.cross(ray, rng.normal(0, 1, (m, 3)))
+        perp /= np.maximum(np.linalg.norm(perp, axis=1), 1e-9)[:, None]
+        normal = np.cos(ang)[:, None] * ray + np.sin(ang)[:, None] * perp
+        for j in range(m):
+            if src[j] >= 0:
+                normal[j] = normal[src[j]]
+        # keypoints: random ones, then the planted observations in free slots
+        x = rng.uniform(0, float(W), n)
+        y = rng.uniform(0, float(H), n)
+        octv = rng.integers(0, 8, n)
+        desc = rng.integers(0, 256, size=(n, 32), dtype=np.uint8)
+        uright = np.where(rng.random(n) < 0.5, x - rng.uniform(5, 100, n), -1.0)
+        free = list(rng.permutation(n))
+        for j in range(m):
+            if not observed[j] or not free:
+                continue
+            i = int(free.pop())
+            ps = int(min(7, max(0, np.ceil(np.log(max(mscale[j], 1e-9)) / np.log(1.2)))))
+            oc = min(7, max(0, ps + int(rng.choice([-1, 0, 0, 1, 3]))))
+            s = (0.8 if rng.random() < 0.92 else 2.5) * 1.2 ** oc
+            x[i], y[i], octv[i] = u[j] + rng.normal(0, s), v[j] + rng.normal(0, s), oc
+            desc[i] = flip(mdesc[j], int(rng.integers(0, 46) if rng.random() < 0.92 else rng.integers(46, 71)))
+            if rng.random() < 0.5:
+                uright[i] = 0.0 if rng.random() < 0.03 else max(u[j] - float(bf) / max(z[j], 1e-3) + rng.normal(0, s), 0.0)
+            else:
+                uright[i] = -1.0
+            if rng.random() < 0.08 and free:   # an identical descriptor in another cell of the window
+                rad = 0.6 * th * 1.2 ** max(min(oc, ps), 0)
+                for _ in range(20):
+                    xb, yb = x[i] + rng.uniform(-rad, rad), y[i] + rng.uniform(-rad, rad)
+                    if cell(xb, yb) != cell(x[i], y[i]) and 0 <= xb < float(W) and 0 <= yb < float(H):
+                        k = int(free.pop())
+                        x[k], y[k], octv[k], desc[k], uright[k] = xb, yb, oc, desc[i], uright[i]
+                        if uright[i] > 0:
+                            uright[k] = max(uright[i] + (xb - x[i]), 0.0)
+                        first, second = (i, k) if cell(x[i], y[i]) < cell(xb, yb) else (k, i)
+                        if first < second:   # the scan-first keypoint takes the higher index
+                            for arr in (x, y, uright):
+                                arr[first], arr[second] = arr[second], arr[first]
+                        break
+        F["kp_xy"].append(np.stack([x, y], 1).astype(np.float32))
+        F["kp_octave"].append(octv.astype(np.int32))
+        F["kp_uright"].append(uright.astype(np.float32))
+        F["kp_desc"].append(desc)
+        F["kp_claimed"].append((rng.random(n) < claimed_frac).astype(np.uint8))
+        F["bounds"].append(np.array([[0.0, W, 0.0, H]], np.float32))
+        F["pose"].append(np.concatenate([Rcw.reshape(-1), tcw])[None].astype(np.float32))
+        F["camera"].append(np.array([[fx, fy, cx, cy, bf]], np.float32))
+        F["mp_valid"].append((rng.random(m) < 0.9).astype(np.uint8))
+        F["mp_xw"].append(Xw)
+        F["mp_max_min"].append(np.stack([maxd, mind], 1).astype(np.float32))
+        F["mp_normal"].append(normal.astype(np.float32))
+        F["mp_desc"].append(mdesc)
+    shapes = dict(kp_xy=(0, 2), kp_octave=(0,), kp_uright=(0,), kp_desc=(0, 32), kp_claimed=(0,), bounds=(0, 4),
+                  pose=(0, 12), camera=(0, 5), mp_valid=(0,), mp_xw=(0, 3), mp_max_min=(0, 2), mp_normal=(0, 3),
+                  mp_desc=(0, 32))
+    out = {}
+    for k, shape in shapes.items():
+        dt = np.uint8 if k in ("kp_desc", "mp_desc", "kp_claimed", "mp_valid") else (np.int32 if k == "kp_octave" else np.float32)
+        out[k] = np.ascontiguousarray(np.concatenate(F[k]).astype(dt) if F[k] else np.zeros(shape, dt))
+    out["kp_begin"] = np.concatenate([[0], np.cumsum(kps)]).astype(np.int32)
+    out["mp_begin"] = np.concatenate([[0], np.cumsum(mps)]).astype(np.int32)
+    out.update(scale_factors=cum, inv_sigma2=(np.float32(1) / (cum * cum)).astype(np.float32),
+               log_scale_factor=float(np.float32(np.log(np.float64(np.float32(1.2))))), th=float(th),
+               chi2_gate=bool(chi2_gate))
+    return out
