@@ -530,6 +530,89 @@ int orbm_search_by_projection_sim3(const orbm_fuse_batch* b, const uint8_t* kp_c
 int orbm_search_by_projection_sim3_device(const orbm_fuse_batch* b, const uint8_t* kp_claimed, int32_t* kp_match,
                                           int32_t* n_matches, void* stream);
 
+/* int ORBmatcher::SearchBySim3(KeyFrame* keyframe1, KeyFrame* keyframe2, std::vector<MapPoint*>& matches12,
+ * const Sim3& S12, float th) (src/ORBmatcher.cc:1090-1277; LoopClosing::FindLoopInCandidateKFs,
+ * LoopClosing.cc:137, th 7.5), batched over (keyframe1, keyframe2, S12) pairs.  Pair p: side s in {1, 2} has
+ * the keypoint slots [kp{s}_begin[p], kp{s}_begin[p+1]) (keypointsUn pt / octave, descriptorsL rows), the
+ * keyframe's imageBounds, GetPose() (Rcw then tcw) and intrinsics, and one map point row per slot.
+ * mp1_valid[i1] = mappoints1[i1] && !matches12[i1] && !mappoints1[i1]->isBad() (:1130) and mp2_valid[i2] =
+ * mappoints2[i2] && !alreadyMatched2[i2] && !mappoints2[i2]->isBad() (:1197, alreadyMatched2 from
+ * GetIndexInKeyFrame(keyframe2) over the incoming matches12, :1111-1121), both evaluated on entry; for a
+ * valid slot mp_xw = GetWorldPos(), mp_max_min = (maxDistance_, minDistance_) raw, mp_desc =
+ * GetDescriptor() (the map point's descriptor, not the slot's keypoint row).  s12 = S12's R (row-major), t, s.
+ * On the device, in the reference's order and float expressions, for every valid slot of keyframe 1:
+ * Xc1 = R1w * Xw + t1w, Xc2 = S21.Map(Xc1) with S21 = S12.Inverse() derived there (Sim3.h:40-47: (s * R) * x
+ * + t; R21 = R12^T, t21 = ((-(1 / s)) * R12^T) * t12, s21 = 1 / s), Xc2.z < 0 rejects (:1138), CameraToImage
+ * with keyframe 2's intrinsics and its half-open bounds (:1141-1147), dist3D = (float)cv::norm(Xc2) against
+ * 0.8f * minDistance_ / 1.2f * maxDistance_ (:1149-1155; no viewing-angle and no chi2 gate), PredictScale
+ * (MapPoint.cc:394-403), the window GetFeaturesInArea(u, v, th * scaleFactors[predictedScale]) on keyframe
+ * 2's grid, the levels [predictedScale - 1, predictedScale], the first minimum descriptor distance in scan
+ * order, and match1[i1] = bestIdx iff bestDist <= TH_HIGH (100) (:1163-1190).  The mirror image with
+ * S12.Map gives match2 (:1194-1258).  match12[i1] = match1[i1] iff match1[i1] >= 0 && match2[match1[i1]]
+ * == i1, else -1 (:1261-1274).  Nothing is claimed during the loops, so no slot depends on another; the
+ * caller then writes matches12[i1] = mappoints2[match12[i1]]. */
+typedef struct orbm_sim3_batch {
+    int32_t        n_pairs, total_kp1, total_kp2;
+    const int32_t* kp1_begin;    /* n_pairs + 1 */
+    const int32_t* kp2_begin;    /* n_pairs + 1 */
+    const float*   kp1_xy;       /* keyframe 1 keypointsUn pt, total_kp1 x 2 */
+    const int32_t* kp1_octave;
+    const uint8_t* kp1_desc;     /* total_kp1 x 32 */
+    const float*   kp2_xy;       /* keyframe 2, total_kp2 rows */
+    const int32_t* kp2_octave;
+    const uint8_t* kp2_desc;
+    const float*   bounds1;      /* n_pairs x 4: imageBounds minx, maxx, miny, maxy */
+    const float*   pose1;        /* n_pairs x 12: Rcw (row-major 3x3) then tcw */
+    const float*   camera1;      /* n_pairs x 4: fx, fy, cx, cy */
+    const float*   bounds2;
+    const float*   pose2;
+    const float*   camera2;
+    const uint8_t* mp1_valid;    /* total_kp1 */
+    const float*   mp1_xw;       /* total_kp1 x 3 */
+    const float*   mp1_max_min;  /* total_kp1 x 2: maxDistance_, minDistance_ */
+    const uint8_t* mp1_desc;     /* total_kp1 x 32 */
+    const uint8_t* mp2_valid;    /* total_kp2 rows */
+    const float*   mp2_xw;
+    const float*   mp2_max_min;
+    const uint8_t* mp2_desc;
+    const float*   s12;          /* n_pairs x 13: R12 (row-major 3x3), t12, s */
+    int32_t        n_levels;
+    const float*   scale_factors;/* host, n_levels (pyramid.scaleFactors) */
+    float          log_scale_factor;
+    float          th;
+} orbm_sim3_batch;
+
+/* match12 [total_kp1]: keyframe-2-relative index agreed for slot i1 or -1; match1 [total_kp1] / match2
+ * [total_kp2]: the one-way results (may be NULL); n_found[p]: the return value, the count of match12 >= 0.
+ * Host entry: every pointer is host memory, synchronous, offsets validated; a keyframe with more than
+ * ORBM_PROJ_MAX_KP keypoints is refused. */
+int orbm_search_by_sim3(const orbm_sim3_batch* b, int32_t* match12, int32_t* match1, int32_t* match2,
+                        int32_t* n_found, int device);
+/* Device entry: every array in HBM except scale_factors; enqueue only on `stream`.  A pair either of whose
+ * keyframes has more than ORBM_PROJ_MAX_KP keypoints gets n_found = -1 and every match* of the pair -1;
+ * the other pairs are unaffected. */
+int orbm_search_by_sim3_device(const orbm_sim3_batch* b, int32_t* match12, int32_t* match1, int32_t* match2,
+                               int32_t* n_found, void* stream);
+
+/* void MapPoint::ComputeDistinctiveDescriptors() (src/MapPoint.cc:257-320; after every AddObservation and at
+ * the end of Replace; LocalMapping::SearchInNeighbors runs one per map point of the keyframe,
+ * LocalMapping.cc:626-635), batched over map points.  Point p holds the rows [begin[p], begin[p+1]) of
+ * desc: its observations' descriptorsL.row(idx) from non-bad keyframes, gathered in the reference's
+ * iteration order.  best[p] = the point-relative row with the least median Hamming distance to the rows
+ * of the point, the median being sorted(row of the N x N matrix, zero diagonal included)[(N - 1) / 2] and
+ * the lowest row winning a tie (:300-314); best_median[p] = that median; out_desc[p] = the winning row.
+ * An empty point gets best = best_median = -1 and its out_desc row is not written, so out_desc may be the
+ * caller's resident map point descriptor array, updated in place. */
+#define ORBM_DISTINCT_MAX_OBS 1024   /* rows per map point */
+/* Host entry: host pointers, synchronous; a point with more than ORBM_DISTINCT_MAX_OBS rows is refused. */
+int orbm_distinctive_descriptors(const uint8_t* desc /* total x 32 */, const int32_t* begin /* n_points + 1 */,
+                                 int32_t n_points, int32_t* best, int32_t* best_median /* or NULL */,
+                                 uint8_t* out_desc /* n_points x 32 or NULL */, int device);
+/* Device entry: every array in HBM; enqueue only on `stream`.  A point over the limit gets best =
+ * best_median = -1 and its out_desc row is not written. */
+int orbm_distinctive_descriptors_device(const uint8_t* desc, const int32_t* begin, int32_t n_points, int32_t* best,
+                                        int32_t* best_median, uint8_t* out_desc, void* stream);
+
 /* int ORBmatcher::SearchForInitialization(Frame& F1, Frame& F2, std::vector<cv::Point2f>& vbPrevMatched,
  * std::vector<int>& vnMatches12, int windowSize) (include/ORBmatcher.h:81, src/ORBmatcher.cc:614-694;
  * Tracking::MonocularInitialization, Tracking.cc:1052), batched over initialisation pairs.

@@ -445,6 +445,47 @@ inline void SearchByProjectionSim3Batch(const orbm_fuse_batch& b, const uint8_t*
           "orbm_search_by_projection_sim3_device");
 }
 
+// int ORBmatcher::SearchBySim3(KeyFrame*, KeyFrame*, std::vector<MapPoint*>& matches12, const Sim3& S12, float th)
+// (src/ORBmatcher.cc:1090-1277), batched over (keyframe1, keyframe2, S12) pairs on HBM arrays
+// (orbm_sim3_batch: the caller marks mp1_valid = mappoints1[i1] && !matches12[i1] && !isBad() and mp2_valid =
+// mappoints2[i2] && !alreadyMatched2[i2] && !isBad() on entry).  Enqueue only; match12[i1] = the agreed
+// keyframe-2 index or -1 (d_match1 / d_match2, the one-way results, may be nullptr).  The caller then writes
+// matches12[i1] = mappoints2[match12[i1]] (:1270).
+inline void SearchBySim3Batch(const orbm_sim3_batch& b, int32_t* d_match12, int32_t* d_match1, int32_t* d_match2,
+                              int32_t* d_n_found, void* stream = nullptr) {
+    check(orbm_search_by_sim3_device(&b, d_match12, d_match1, d_match2, d_n_found, stream), "orbm_search_by_sim3_device");
+}
+// The same for one pair on host arrays; returns nfound.
+inline int SearchBySim3(const orbm_sim3_batch& b, std::vector<int32_t>& match12, int device = 0) {
+    if (b.n_pairs != 1) throw std::invalid_argument("SearchBySim3: one pair per call (use the batch form)");
+    match12.assign(std::max(b.total_kp1, 1), -1);
+    int32_t nf = 0;
+    check(orbm_search_by_sim3(&b, match12.data(), nullptr, nullptr, &nf, device), "orbm_search_by_sim3");
+    match12.resize(b.total_kp1);
+    return nf;
+}
+
+// void MapPoint::ComputeDistinctiveDescriptors() (src/MapPoint.cc:257-320), batched over map points on HBM
+// arrays: point p holds the rows [begin[p], begin[p + 1]) of d_desc.  Enqueue only; best[p] = the winning
+// point-relative row (-1: empty), d_out_desc[p] = that row (an empty point's row is not written, so
+// d_out_desc may be the resident map point descriptor array); d_best_median and d_out_desc may be nullptr.
+inline void ComputeDistinctiveDescriptorsBatch(const uint8_t* d_desc, const int32_t* d_begin, int32_t n_points,
+                                               int32_t* d_best, int32_t* d_best_median, uint8_t* d_out_desc,
+                                               void* stream = nullptr) {
+    check(orbm_distinctive_descriptors_device(d_desc, d_begin, n_points, d_best, d_best_median, d_out_desc, stream),
+          "orbm_distinctive_descriptors_device");
+}
+// One map point on host rows (descriptors: N x 32 bytes in the reference's iteration order); returns bestIdx
+// (-1 when N == 0) and copies the winning row to `descriptor` (32 bytes, untouched when N == 0).
+inline int ComputeDistinctiveDescriptors(const std::vector<uint8_t>& descriptors, uint8_t* descriptor, int device = 0) {
+    if (descriptors.size() % 32) throw std::invalid_argument("ComputeDistinctiveDescriptors: rows of 32 bytes");
+    const int32_t begin[2] = {0, static_cast<int32_t>(descriptors.size() / 32)};
+    int32_t best = -1;
+    check(orbm_distinctive_descriptors(descriptors.data(), begin, 1, &best, nullptr, descriptor, device),
+          "orbm_distinctive_descriptors");
+    return best;
+}
+
 // DBoW2 ORBVocabulary: loadFromTextFile + transform(features, BowVector&, FeatureVector&, levelsup)
 // (TemplatedVocabulary.h:1130-1196, :1341-1431) with the reference's container types.
 class ORBVocabulary {

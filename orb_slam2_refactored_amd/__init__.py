@@ -9,10 +9,12 @@ All compute runs in liborbslam2_amd.so (HIP kernels behind include/orbslam2_amd.
 """
 from .extractor import ORBextractor, KP_DTYPE
 from .matcher import (ORBmatcher, ComputeStereoMatches, Fuse, fuse_device, SearchByProjectionSim3,
-                      search_by_projection_sim3_device)
+                      search_by_projection_sim3_device, SearchBySim3, search_by_sim3_device,
+                      ComputeDistinctiveDescriptors, compute_distinctive_descriptors_device)
 from . import optimizer
 from .synth import synth_image, shifted_pair, stereo_pair, make_pose_batch
 
 __all__ = ["ORBextractor", "ORBmatcher", "ComputeStereoMatches", "Fuse", "fuse_device", "SearchByProjectionSim3",
-           "search_by_projection_sim3_device", "optimizer", "KP_DTYPE", "synth_image", "shifted_pair", "stereo_pair",
+           "search_by_projection_sim3_device", "SearchBySim3", "search_by_sim3_device", "ComputeDistinctiveDescriptors",
+           "compute_distinctive_descriptors_device", "optimizer", "KP_DTYPE", "synth_image", "shifted_pair", "stereo_pair",
            "make_pose_batch"]

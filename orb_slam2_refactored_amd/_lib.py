@@ -112,6 +112,20 @@ class FuseBatch(C.Structure):
                 ("th", C.c_float), ("chi2_gate", C.c_int32)]
 
 
+class Sim3Batch(C.Structure):
+    """orbm_sim3_batch (include/orbslam2_amd.h)."""
+    _fields_ = [("n_pairs", C.c_int32), ("total_kp1", C.c_int32), ("total_kp2", C.c_int32),
+                ("kp1_begin", C.c_void_p), ("kp2_begin", C.c_void_p),
+                ("kp1_xy", C.c_void_p), ("kp1_octave", C.c_void_p), ("kp1_desc", C.c_void_p),
+                ("kp2_xy", C.c_void_p), ("kp2_octave", C.c_void_p), ("kp2_desc", C.c_void_p),
+                ("bounds1", C.c_void_p), ("pose1", C.c_void_p), ("camera1", C.c_void_p),
+                ("bounds2", C.c_void_p), ("pose2", C.c_void_p), ("camera2", C.c_void_p),
+                ("mp1_valid", C.c_void_p), ("mp1_xw", C.c_void_p), ("mp1_max_min", C.c_void_p), ("mp1_desc", C.c_void_p),
+                ("mp2_valid", C.c_void_p), ("mp2_xw", C.c_void_p), ("mp2_max_min", C.c_void_p), ("mp2_desc", C.c_void_p),
+                ("s12", C.c_void_p), ("n_levels", C.c_int32), ("scale_factors", C.c_void_p),
+                ("log_scale_factor", C.c_float), ("th", C.c_float)]
+
+
 class InitBatch(C.Structure):
     """orbm_init_batch (include/orbslam2_amd.h)."""
     _fields_ = [("n_pairs", C.c_int32), ("total_kp", C.c_int32), ("total_q", C.c_int32),
@@ -182,6 +196,10 @@ SIGNATURES = {
     "orbm_fuse_device": (C.c_int, [C.POINTER(FuseBatch), VP, VP, VP, VP]),
     "orbm_search_by_projection_sim3": (C.c_int, [C.POINTER(FuseBatch), VP, VP, VP, C.c_int]),
     "orbm_search_by_projection_sim3_device": (C.c_int, [C.POINTER(FuseBatch), VP, VP, VP, VP]),
+    "orbm_search_by_sim3": (C.c_int, [C.POINTER(Sim3Batch), VP, VP, VP, VP, C.c_int]),
+    "orbm_search_by_sim3_device": (C.c_int, [C.POINTER(Sim3Batch), VP, VP, VP, VP, VP]),
+    "orbm_distinctive_descriptors": (C.c_int, [VP, VP, C.c_int32, VP, VP, VP, C.c_int]),
+    "orbm_distinctive_descriptors_device": (C.c_int, [VP, VP, C.c_int32, VP, VP, VP, VP]),
     "orbv_load_text": (C.c_int, [C.c_char_p, C.c_int, C.POINTER(VP)]),
     "orbv_create": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, VP, VP, VP, VP, C.c_int, C.POINTER(VP)]),
     "orbv_destroy": (C.c_int, [VP]),

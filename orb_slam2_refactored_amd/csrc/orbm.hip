@@ -1120,6 +1120,8 @@ __global__ __launch_bounds__(256) void search_by_bow_kernel(BowArgs a) {
 
 }  // namespace orbamd
 
+#include "orbm_distinct.h"
+
 using namespace orbamd;
 
 namespace {
@@ -1410,6 +1412,46 @@ int orbm_search_for_triangulation(const orbm_tri_frame* kf1, const orbm_tri_fram
     int nm = 0;
     for (int i = 0; i < n1; i++) nm += match12[i] >= 0;
     if (nmatches) *nmatches = nm;
+    return ORB_OK;
+}
+
+
+int orbm_distinctive_descriptors_device(const uint8_t* desc, const int32_t* begin, int32_t n_points, int32_t* best,
+                                        int32_t* best_median, uint8_t* out_desc, void* stream) {
+    ORB_CHECK_ARG(n_points >= 0, "negative sizes");
+    if (n_points == 0) return ORB_OK;
+    ORB_CHECK_ARG(desc && begin && best, "null argument");
+    return launch_distinct(DistinctArgs{desc, begin, n_points, best, best_median, out_desc}, (hipStream_t)stream);
+}
+
+int orbm_distinctive_descriptors(const uint8_t* desc, const int32_t* begin, int32_t n_points, int32_t* best,
+                                 int32_t* best_median, uint8_t* out_desc, int device) {
+    ORB_CHECK_ARG(n_points >= 0, "negative sizes");
+    if (n_points == 0) return ORB_OK;
+    ORB_CHECK_ARG(begin && best, "null argument");
+    ORB_CHECK_ARG(begin[0] == 0, "begin must start at 0");
+    for (int p = 0; p < n_points; p++) {
+        ORB_CHECK_ARG(begin[p + 1] >= begin[p], "offsets must be non-decreasing");
+        ORB_CHECK_ARG(begin[p + 1] - begin[p] <= ORBM_DISTINCT_MAX_OBS, "map point has more than ORBM_DISTINCT_MAX_OBS observations");
+    }
+    const size_t total = (size_t)begin[n_points], P = (size_t)n_points;
+    ORB_CHECK_ARG(total == 0 || desc, "null descriptors");
+    ORB_HIP_TRY(hipSetDevice(device));
+    HostScratch& s = g_scratch;
+    int rc;
+    const size_t o_bg = align_up(std::max<size_t>(total, 1) * 32, 256), o_bi = o_bg + align_up((P + 1) * 4, 256),
+                 o_bm = o_bi + align_up(P * 4, 256), o_od = o_bm + align_up(P * 4, 256);
+    if ((rc = s.a.reserve(o_od + P * 32))) return rc;
+    char* d = s.a.as<char>();
+    if (total) ORB_HIP_TRY(hipMemcpy(d, desc, total * 32, hipMemcpyHostToDevice));
+    ORB_HIP_TRY(hipMemcpy(d + o_bg, begin, (P + 1) * 4, hipMemcpyHostToDevice));
+    if (out_desc) ORB_HIP_TRY(hipMemcpy(d + o_od, out_desc, P * 32, hipMemcpyHostToDevice));   // empty points keep theirs
+    if ((rc = orbm_distinctive_descriptors_device((const uint8_t*)d, (const int32_t*)(d + o_bg), n_points, (int32_t*)(d + o_bi),
+                                                  (int32_t*)(d + o_bm), out_desc ? (uint8_t*)(d + o_od) : nullptr, nullptr)))
+        return rc;
+    ORB_HIP_TRY(hipMemcpy(best, d + o_bi, P * 4, hipMemcpyDeviceToHost));
+    if (best_median) ORB_HIP_TRY(hipMemcpy(best_median, d + o_bm, P * 4, hipMemcpyDeviceToHost));
+    if (out_desc) ORB_HIP_TRY(hipMemcpy(out_desc, d + o_od, P * 32, hipMemcpyDeviceToHost));
     return ORB_OK;
 }
 

@@ -22,7 +22,8 @@
 //                    wavefront rescans that map point's window against the bitmap.  Then the
 //                    TH_HIGH / same-level ratio test and the claim.
 // The other projection searches below share the grid: the motion-model and relocalisation forms
-// (pjm_*), SearchForInitialization (pi_*), and Fuse / the Sim3 search (orbp_fuse.h).
+// (pjm_*), SearchForInitialization (pi_*), Fuse / the Sim3 search (orbp_fuse.h) and SearchBySim3
+// (orbp_sim3.h).
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -1028,6 +1029,7 @@ static int reloc_common(const orbm_reloc_batch* b, PjArgs& a, RelocExtra& r, Pjm
 }  // namespace orbamd
 
 #include "orbp_fuse.h"
+#include "orbp_sim3.h"
 
 using namespace orbamd;
 
@@ -1492,5 +1494,60 @@ extern "C" int orbm_search_by_projection_sim3(const orbm_fuse_batch* b, const ui
         return rc;
     if (K) ORB_HIP_TRY(hipMemcpy(kp_match, out, (size_t)K * 4, hipMemcpyDeviceToHost));
     ORB_HIP_TRY(hipMemcpy(n_matches, out + o_nm, (size_t)F * 4, hipMemcpyDeviceToHost));
+    return ORB_OK;
+}
+
+
+extern "C" int orbm_search_by_sim3_device(const orbm_sim3_batch* b, int32_t* match12, int32_t* match1, int32_t* match2,
+                                          int32_t* n_found, void* stream) {
+    Sim3Args a;
+    int rc;
+    if ((rc = sim3_common(b, a))) return rc;
+    if (b->n_pairs == 0) return ORB_OK;
+    ORB_CHECK_ARG(n_found && (b->total_kp1 == 0 || match12), "null output array");
+    a.match12 = match12;
+    a.n_found = n_found;
+    int dev = 0;
+    ORB_HIP_TRY(hipGetDevice(&dev));
+    if (g_pj.device != dev) {
+        g_pj.ws.release();
+        g_pj.io.release();
+        g_pj.device = dev;
+    }
+    if ((rc = g_pj.ws.reserve(sim3_side_bytes(b->n_pairs, b->total_kp1) + sim3_side_bytes(b->n_pairs, b->total_kp2))))
+        return rc;
+    sim3_carve(a, g_pj.ws.as<char>(), match1, match2);
+    return launch_search_by_sim3(a, (hipStream_t)stream);
+}
+
+extern "C" int orbm_search_by_sim3(const orbm_sim3_batch* b, int32_t* match12, int32_t* match1, int32_t* match2,
+                                   int32_t* n_found, int device) {
+    Sim3Args a;
+    int rc;
+    if ((rc = sim3_common(b, a))) return rc;   // the checks, before any copy
+    const int F = b->n_pairs, K1 = b->total_kp1, K2 = b->total_kp2;
+    if (F == 0) return ORB_OK;
+    ORB_CHECK_ARG(n_found && (K1 == 0 || match12), "null output array");
+    if ((rc = sim3_check_offsets(b))) return rc;
+    ORB_HIP_TRY(hipSetDevice(device));
+    if (g_pj.device != device) {
+        g_pj.ws.release();
+        g_pj.io.release();
+        g_pj.device = device;
+    }
+    const size_t o_m1 = align_up((size_t)std::max(K1, 1) * 4, 256), o_m2 = 2 * o_m1,
+                 o_nf = o_m2 + align_up((size_t)std::max(K2, 1) * 4, 256);
+    orbm_sim3_batch d;
+    char* out;
+    if ((rc = sim3_upload(b, g_pj.io, o_nf + (size_t)F * 4, d, out))) return rc;
+    if ((rc = orbm_search_by_sim3_device(&d, (int32_t*)out, (int32_t*)(out + o_m1), (int32_t*)(out + o_m2),
+                                         (int32_t*)(out + o_nf), nullptr)))
+        return rc;
+    if (K1) {
+        ORB_HIP_TRY(hipMemcpy(match12, out, (size_t)K1 * 4, hipMemcpyDeviceToHost));
+        if (match1) ORB_HIP_TRY(hipMemcpy(match1, out + o_m1, (size_t)K1 * 4, hipMemcpyDeviceToHost));
+    }
+    if (K2 && match2) ORB_HIP_TRY(hipMemcpy(match2, out + o_m2, (size_t)K2 * 4, hipMemcpyDeviceToHost));
+    ORB_HIP_TRY(hipMemcpy(n_found, out + o_nf, (size_t)F * 4, hipMemcpyDeviceToHost));
     return ORB_OK;
 }

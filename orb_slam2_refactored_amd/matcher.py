@@ -690,3 +690,146 @@ def search_by_projection_sim3_device(batch: dict, kp_match=None, n_matches=None,
                                                       tptr(kp_match), tptr(n_matches), stream_ptr(stream)),
           "orbm_search_by_projection_sim3_device")
     return kp_match, n_matches
+
+
+_SIM3_KEYS = (("kp1_begin", np.int32), ("kp2_begin", np.int32),
+              ("kp1_xy", np.float32), ("kp1_octave", np.int32), ("kp1_desc", np.uint8),
+              ("kp2_xy", np.float32), ("kp2_octave", np.int32), ("kp2_desc", np.uint8),
+              ("bounds1", np.float32), ("pose1", np.float32), ("camera1", np.float32),
+              ("bounds2", np.float32), ("pose2", np.float32), ("camera2", np.float32),
+              ("mp1_valid", np.uint8), ("mp1_xw", np.float32), ("mp1_max_min", np.float32), ("mp1_desc", np.uint8),
+              ("mp2_valid", np.uint8), ("mp2_xw", np.float32), ("mp2_max_min", np.float32), ("mp2_desc", np.uint8),
+              ("s12", np.float32))
+# K1 / K2 = total keypoint slots of keyframes 1 / 2; every map point array has one row per slot
+_SIM3_ROWS = {"kp1_begin": ("F1", 1), "kp2_begin": ("F1", 1), "s12": ("F", 13),
+              **{f"{k}{s}": ("F", n) for s in "12" for k, n in (("bounds", 4), ("pose", 12), ("camera", 4))},
+              **{f"kp{s}_{k}": (f"K{s}", n) for s in "12" for k, n in (("xy", 2), ("octave", 1), ("desc", 32))},
+              **{f"mp{s}_{k}": (f"K{s}", n) for s in "12" for k, n in (("valid", 1), ("xw", 3), ("max_min", 2), ("desc", 32))}}
+
+
+def _sim3_check(batch, dims, what):
+    """Every orbm_sim3_batch array present and long enough."""
+    for k, _ in _SIM3_KEYS:
+        if batch.get(k) is None:
+            raise ValueError(f"{what}: {k} is required")
+    _check_batch_rows(batch, [k for k, _ in _SIM3_KEYS], dims, what, _SIM3_ROWS)
+
+
+def _sim3_struct(batch, conv, F, K1, K2):
+    from ._lib import Sim3Batch
+    sf = np.ascontiguousarray(batch["scale_factors"], np.float32)
+    sb = Sim3Batch(F, K1, K2, *[conv(batch[k], dt) for k, dt in _SIM3_KEYS], len(sf), ptr(sf),
+                   float(batch["log_scale_factor"]), float(batch["th"]))
+    return sb, sf
+
+
+def SearchBySim3(batch: dict, device: int = 0):
+    """ORBmatcher::SearchBySim3(keyframe1, keyframe2, matches12, S12, th) (src/ORBmatcher.cc:1090-1277,
+    LoopClosing.cc:137) batched over (keyframe1, keyframe2, S12) pairs on host arrays (orbm_sim3_batch
+    fields; mp1_valid / mp2_valid are the skip tests on entry).  Returns (match12 [total_kp1] = the agreed
+    keyframe-2 index of each slot of keyframe 1 or -1, match1 [total_kp1], match2 [total_kp2] = the one-way
+    results, n_found [n_pairs] = the return value).  The caller writes matches12[i1] =
+    mappoints2[match12[i1]] (INTEGRATION.md)."""
+    for k in ("kp1_begin", "kp2_begin"):
+        if batch.get(k) is None:
+            raise ValueError(f"SearchBySim3: {k} is required")
+    F = len(batch["kp1_begin"]) - 1
+    K1, K2 = int(batch["kp1_begin"][-1]), int(batch["kp2_begin"][-1])
+    _sim3_check(batch, {"F": F, "F1": F + 1, "K1": K1, "K2": K2}, "SearchBySim3")
+    keep = []
+    sb, _host = _sim3_struct(batch, _host_conv(keep), F, K1, K2)
+    m12 = np.empty(max(K1, 1), np.int32)
+    m1 = np.empty(max(K1, 1), np.int32)
+    m2 = np.empty(max(K2, 1), np.int32)
+    nf = np.empty(max(F, 1), np.int32)
+    check(lib().orbm_search_by_sim3(C.byref(sb), ptr(m12), ptr(m1), ptr(m2), ptr(nf), int(device)), "orbm_search_by_sim3")
+    return m12[:K1], m1[:K1], m2[:K2], nf[:F]
+
+
+def search_by_sim3_device(batch: dict, match12=None, match1=None, match2=None, n_found=None, stream=None):
+    """Device form of SearchBySim3: GPU tensors for the orbm_sim3_batch arrays, host values for
+    scale_factors, log_scale_factor and th.  n_found[p] = -1 (and every match of the pair -1) when a
+    keyframe of the pair has more than ORBM_PROJ_MAX_KP keypoints."""
+    import torch
+    for k in ("kp1_begin", "kp2_begin", "kp1_xy", "kp2_xy"):
+        if batch.get(k) is None:
+            raise ValueError(f"search_by_sim3_device: {k} is required")
+    kb = batch["kp1_begin"]
+    F = kb.numel() - 1
+    _check_device_dtypes(batch, _SIM3_KEYS, "search_by_sim3_device")
+    K1, K2 = int(batch["kp1_xy"].shape[0]), int(batch["kp2_xy"].shape[0])
+    _sim3_check(batch, {"F": F, "F1": F + 1, "K1": K1, "K2": K2}, "search_by_sim3_device")
+    new = lambda n: torch.empty(max(n, 1), dtype=torch.int32, device=kb.device)   # noqa: E731
+    match12 = new(K1) if match12 is None else match12
+    match1 = new(K1) if match1 is None else match1
+    match2 = new(K2) if match2 is None else match2
+    n_found = new(F) if n_found is None else n_found
+    sb, _host = _sim3_struct(batch, lambda t, dt: tptr(t), F, K1, K2)
+    check(lib().orbm_search_by_sim3_device(C.byref(sb), tptr(match12), tptr(match1), tptr(match2), tptr(n_found),
+                                           stream_ptr(stream)), "orbm_search_by_sim3_device")
+    return match12, match1, match2, n_found
+
+
+_DISTINCT_KEYS = (("desc", np.uint8), ("begin", np.int32))
+
+
+def ComputeDistinctiveDescriptors(desc, begin, out_desc=None, device: int = 0):
+    """MapPoint::ComputeDistinctiveDescriptors (src/MapPoint.cc:257-320) batched over map points on host
+    arrays: point p holds the rows desc[begin[p]:begin[p + 1]] (its observations' descriptors in the
+    reference's iteration order).  Returns (best [n_points] = the point-relative winning row, -1 for an
+    empty point; best_median [n_points]; out_desc [n_points, 32] = the winning rows).  `out_desc`, when
+    given, is updated in place: the rows of empty points keep their content (else they are zero)."""
+    batch = {"desc": desc, "begin": begin}
+    for k in ("desc", "begin"):
+        if batch[k] is None:
+            raise ValueError(f"ComputeDistinctiveDescriptors: {k} is required")
+    begin = np.ascontiguousarray(begin, np.int32)
+    if begin.size < 1:
+        raise ValueError("ComputeDistinctiveDescriptors: begin needs n_points + 1 entries")
+    P, T = begin.size - 1, int(begin[-1])
+    rows = {"desc": ("T", 32), "begin": ("P1", 1), "out_desc": ("P", 32)}
+    batch["out_desc"] = out_desc
+    _check_batch_rows(batch, ("desc", "begin", "out_desc"), {"T": T, "P1": P + 1, "P": P},
+                      "ComputeDistinctiveDescriptors", rows)
+    desc = np.ascontiguousarray(desc, np.uint8)
+    if out_desc is None:
+        out_desc = np.zeros((P, 32), np.uint8)
+    elif not (isinstance(out_desc, np.ndarray) and out_desc.dtype == np.uint8 and out_desc.flags.c_contiguous
+              and out_desc.flags.writeable):
+        raise ValueError("ComputeDistinctiveDescriptors: out_desc must be a writable contiguous uint8 array")
+    best = np.empty(max(P, 1), np.int32)
+    med = np.empty(max(P, 1), np.int32)
+    check(lib().orbm_distinctive_descriptors(ptr(desc), ptr(begin), P, ptr(best), ptr(med), ptr(out_desc), int(device)),
+          "orbm_distinctive_descriptors")
+    return best[:P], med[:P], out_desc
+
+
+def compute_distinctive_descriptors_device(desc, begin, best=None, best_median=None, out_desc=None, stream=None):
+    """Device form of ComputeDistinctiveDescriptors: GPU tensors desc [total, 32] uint8 and begin
+    [n_points + 1] int32 (begin[-1] <= total is the caller's contract: it is not read back).  `out_desc`
+    may be the resident map point descriptor tensor: the rows of empty points, and of points with more
+    than ORBM_DISTINCT_MAX_OBS rows (best = -1), are left as they are."""
+    import torch
+    batch = {"desc": desc, "begin": begin, "best": best, "best_median": best_median, "out_desc": out_desc}
+    for k in ("desc", "begin"):
+        if batch[k] is None:
+            raise ValueError(f"compute_distinctive_descriptors_device: {k} is required")
+    _check_device_dtypes(batch, _DISTINCT_KEYS + (("best", np.int32), ("best_median", np.int32), ("out_desc", np.uint8)),
+                         "compute_distinctive_descriptors_device")
+    if begin.numel() < 1:
+        raise ValueError("compute_distinctive_descriptors_device: begin needs n_points + 1 entries")
+    P = begin.numel() - 1
+    rows = {"best": ("P", 1), "best_median": ("P", 1), "out_desc": ("P", 32)}
+    _check_batch_rows(batch, ("best", "best_median", "out_desc"), {"P": P}, "compute_distinctive_descriptors_device", rows)
+    if desc.numel() % 32:
+        raise ValueError("compute_distinctive_descriptors_device: desc must hold 32-byte rows")
+    if best is None:
+        best = torch.empty(max(P, 1), dtype=torch.int32, device=begin.device)
+    if best_median is None:
+        best_median = torch.empty(max(P, 1), dtype=torch.int32, device=begin.device)
+    if out_desc is None:
+        out_desc = torch.zeros((max(P, 1), 32), dtype=torch.uint8, device=begin.device)
+    check(lib().orbm_distinctive_descriptors_device(tptr(desc), tptr(begin), P, tptr(best), tptr(best_median),
+                                                    tptr(out_desc), stream_ptr(stream)),
+          "orbm_distinctive_descriptors_device")
+    return best, best_median, out_desc

@@ -811,3 +811,163 @@ def make_fuse_batch(seed: int = 0, n_items: int = 4, n_kp=2000, n_mp=1500, th: f
                log_scale_factor=float(np.float32(np.log(np.float64(np.float32(1.2))))), th=float(th),
                chi2_gate=bool(chi2_gate))
     return out
+
+
+def make_sim3_batch(seed: int = 0, n_pairs: int = 4, n_kp1=2000, n_kp2=2000, th: float = 7.5, scale=None):
+    """ORBmatcher::SearchBySim3 inputs (orbm_sim3_batch, host arrays) shaped like
+    LoopClosing::FindLoopInCandidateKFs (LoopClosing.cc:137, th 7.5) on the KITTI camera.  Per pair two
+    keyframes with their own poses in two maps related by S12 (a few degrees, ~0.5 m, s = `scale`, or drawn
+    from U(0.7, 0.95) / U(1.05, 1.4) when None: never 1), and a shared 3-D structure of min(n_kp1, n_kp2)
+    / 2 points defined in camera 2 (z in 4..40 m, projections up to 10 px outside the image; 2 % behind the
+    camera).  Every shared point holds a slot in both keyframes:
+      the keypoint sits at the point's projection plus N(0, 1.2^octave) px of jitter (well under the
+      radius th * 1.2^scale), octave = the scale predicted from the other side + {0, 0, 0, 0, -1, -1, 1, -2} (the
+      last two fall outside the level window), its descriptor 0-40 bits off the shared one (90 %) or
+      90-130 bits (best distances above TH_HIGH);
+      the map point has maxDistance_ = dist * 1.2^o * U(0.9, 1.1) (3 %: dist / 2 or dist * 6, outside the
+      invariance range), a descriptor 0-6 bits off the shared one, and is valid with probability 0.85
+      (the rest: no map point, or matched on entry);
+      6 % get a keypoint with the identical descriptor in another grid cell of the window of the other
+      keyframe, the one earlier in scan order holding the higher index (a tie index order would decide
+      the other way); 6 % get a decoy in keyframe 1 closer to keyframe 2's map point descriptor than the
+      true keypoint (a 1 -> 2 match without its 2 -> 1 partner); 6 % a keypoint with the identical
+      descriptor just outside the radius.
+    The other slots are random keypoints, half of them holding a random map point in front of the camera.
+    n_kp1 / n_kp2: int or per-pair list."""
+    rng = np.random.default_rng(seed)
+    kps = [[int(n)] * n_pairs if np.isscalar(n) else [int(v) for v in n] for n in (n_kp1, n_kp2)]
+    fx, fy, cx, cy = (float(np.float32(KITTI[k])) for k in ("fx", "fy", "cx", "cy"))
+    W, H = float(KITTI["width"]), float(KITTI["height"])
+    cum = np.ones(8, np.float32)
+    for i in range(1, 8):
+        cum[i] = np.float32(cum[i - 1] * np.float32(1.2))
+    invW, invH = np.float32(64) / np.float32(W), np.float32(48) / np.float32(H)
+
+    def cell(px, py):   # FeaturesGrid::AssignFeatures' cell of a keypoint
+        return (int(np.round(float(invW * np.float32(px)))), int(np.round(float(invH * np.float32(py)))))
+
+    def flip(d, nbits):
+        d = d.copy()
+        for bit in rng.choice(256, size=int(nbits), replace=False):
+            d[bit >> 3] ^= np.uint8(1 << (bit & 7))
+        return d
+
+    def proj(X):
+        return fx * X[0] / X[2] + cx, fy * X[1] / X[2] + cy
+
+    names = ("xy", "octave", "desc", "valid", "xw", "max_min", "mdesc")
+    out = {f"{k}{s}": [] for s in "12" for k in names + ("bounds", "pose", "camera")}
+    out["s12"] = []
+    for p in range(n_pairs):
+        n = [kps[0][p], kps[1][p]]
+        R = [_small_rot(rng, 3.0), _small_rot(rng, 3.0)]
+        t = [rng.normal(0, 2.0, 3), rng.normal(0, 2.0, 3)]
+        R12, t12 = _small_rot(rng, 3.0), rng.normal(0, 0.5, 3)
+        s12 = float(scale) if scale is not None else float(rng.uniform(0.7, 0.95) if rng.random() < 0.5 else rng.uniform(1.05, 1.4))
+        side = []
+        for s in range(2):   # random keypoints; half of the slots hold a random map point
+            m = n[s]
+            z = rng.uniform(4, 40, m)
+            Xc = np.stack([(rng.uniform(0, W, m) - cx) * z / fx, (rng.uniform(0, H, m) - cy) * z / fy, z], 1)
+            dist = np.linalg.norm(Xc, axis=1)
+            maxd = dist * 1.2 ** rng.integers(0, 8, m) * rng.uniform(0.9, 1.1, m)
+            side.append(dict(x=rng.uniform(0, W, m), y=rng.uniform(0, H, m), oct=rng.integers(0, 8, m),
+                             desc=rng.integers(0, 256, size=(m, 32), dtype=np.uint8), valid=(rng.random(m) < 0.5).astype(np.uint8),
+                             xw=(Xc - t[s][None]) @ R[s], maxd=maxd, mdesc=rng.integers(0, 256, size=(m, 32), dtype=np.uint8),
+                             free=list(rng.permutation(m))))
+        for _ in range(min(n) // 2):
+            z = float(rng.uniform(4, 40)) * (-1.0 if rng.random() < 0.02 else 1.0)
+            Xc2 = np.array([(rng.uniform(-10, W + 10) - cx) * z / fx, (rng.uniform(-4, H + 4) - cy) * z / fy, z])
+            Xc = [s12 * (R12 @ Xc2) + t12, Xc2]   # the point in camera 1 and in camera 2
+            D = rng.integers(0, 256, size=32, dtype=np.uint8)
+            slot = [int(side[s]["free"].pop()) for s in range(2)]
+            o = [int(rng.integers(0, 7)), int(rng.integers(0, 7))]
+            for s in range(2):   # the map point of side s is searched in the other keyframe, at distance |Xc[1 - s]|
+                S, i = side[s], slot[s]
+                far = float(np.linalg.norm(Xc[1 - s]))
+                kind = rng.random()
+                mscale = 1.2 ** o[s] * rng.uniform(0.9, 1.1) if kind >= 0.03 else (0.5 if kind < 0.015 else 6.0)
+                S["xw"][i] = R[s].T @ (Xc[s] - t[s])
+                S["maxd"][i] = far * mscale
+                S["mdesc"][i] = flip(D, rng.integers(0, 7))
+                S["valid"][i] = 1 if rng.random() < 0.85 else 0
+            for s in range(2):   # the keypoint of side s is what the other side's map point should find
+                S, i = side[s], slot[s]
+                if Xc[s][2] <= 0.1:
+                    continue
+                u, v = proj(Xc[s])
+                ps = int(min(7, max(0, np.ceil(np.log(max(side[1 - s]["maxd"][slot[1 - s]] / np.linalg.norm(Xc[s]), 1e-9)) / np.log(1.2)))))
+                oc = min(7, max(0, ps + int(rng.choice([0, 0, 0, 0, -1, -1, 1, -2]))))
+                S["x"][i], S["y"][i], S["oct"][i] = u + rng.normal(0, 1.2 ** oc), v + rng.normal(0, 1.2 ** oc), oc
+                S["desc"][i] = flip(D, rng.integers(0, 41) if rng.random() < 0.9 else rng.integers(90, 131))
+                rad = th * 1.2 ** ps
+                extra = rng.random()
+                if extra < 0.06 and S["free"]:   # an identical descriptor in another cell of the window
+                    for _try in range(20):
+                        xb, yb = S["x"][i] + rng.uniform(-0.5, 0.5) * rad, S["y"][i] + rng.uniform(-0.5, 0.5) * rad
+                        if cell(xb, yb) != cell(S["x"][i], S["y"][i]) and 0 <= xb < W and 0 <= yb < H:
+                            k = int(S["free"].pop())
+                            S["x"][k], S["y"][k], S["oct"][k], S["desc"][k] = xb, yb, oc, S["desc"][i]
+                            first, second = (i, k) if cell(S["x"][i], S["y"][i]) < cell(xb, yb) else (k, i)
+                            if first < second:   # the scan-first keypoint takes the higher index
+                                for arr in (S["x"], S["y"]):
+                                    arr[first], arr[second] = arr[second], arr[first]
+                            break
+                elif extra < 0.12 and s == 0 and S["free"]:   # a decoy for the 2 -> 1 search
+                    k = int(S["free"].pop())
+                    S["x"][k], S["y"][k], S["oct"][k] = u + rng.normal(0, 1.0), v + rng.normal(0, 1.0), max(0, min(ps, 7))
+                    S["desc"][k] = side[1]["mdesc"][slot[1]]
+                elif extra < 0.18 and S["free"]:   # the identical descriptor just outside the radius
+                    k = int(S["free"].pop())
+                    S["x"][k], S["y"][k], S["oct"][k], S["desc"][k] = u + rad * 1.05 + 1.0, v, oc, S["desc"][i]
+        for s, tag in enumerate("12"):
+            S = side[s]
+            out["xy" + tag].append(np.stack([S["x"], S["y"]], 1).astype(np.float32).reshape(-1, 2))
+            out["octave" + tag].append(S["oct"].astype(np.int32))
+            out["desc" + tag].append(S["desc"])
+            out["valid" + tag].append(S["valid"])
+            out["xw" + tag].append(S["xw"].astype(np.float32).reshape(-1, 3))
+            out["max_min" + tag].append(np.stack([S["maxd"], S["maxd"] / float(cum[7])], 1).astype(np.float32).reshape(-1, 2))
+            out["mdesc" + tag].append(S["mdesc"])
+            out["bounds" + tag].append(np.array([[0.0, W, 0.0, H]], np.float32))
+            out["pose" + tag].append(np.concatenate([R[s].reshape(-1), t[s]])[None].astype(np.float32))
+            out["camera" + tag].append(np.array([[fx, fy, cx, cy]], np.float32))
+        out["s12"].append(np.concatenate([R12.reshape(-1), t12, [s12]])[None].astype(np.float32))
+    cat = lambda xs, shape, dt: np.ascontiguousarray(np.concatenate(xs).astype(dt) if xs else np.zeros(shape, dt))   # noqa: E731
+    b = {"s12": cat(out["s12"], (0, 13), np.float32)}
+    for s, tag in enumerate("12"):
+        b[f"kp{tag}_begin"] = np.concatenate([[0], np.cumsum(kps[s])]).astype(np.int32)
+        b[f"kp{tag}_xy"] = cat(out["xy" + tag], (0, 2), np.float32)
+        b[f"kp{tag}_octave"] = cat(out["octave" + tag], (0,), np.int32)
+        b[f"kp{tag}_desc"] = cat(out["desc" + tag], (0, 32), np.uint8)
+        b[f"mp{tag}_valid"] = cat(out["valid" + tag], (0,), np.uint8)
+        b[f"mp{tag}_xw"] = cat(out["xw" + tag], (0, 3), np.float32)
+        b[f"mp{tag}_max_min"] = cat(out["max_min" + tag], (0, 2), np.float32)
+        b[f"mp{tag}_desc"] = cat(out["mdesc" + tag], (0, 32), np.uint8)
+        for k, w in (("bounds", 4), ("pose", 12), ("camera", 4)):
+            b[k + tag] = cat(out[k + tag], (0, w), np.float32)
+    b.update(scale_factors=cum, log_scale_factor=float(np.float32(np.log(np.float64(np.float32(1.2))))), th=float(th))
+    return b
+
+
+def make_observation_sets(seed: int = 0, n_points: int = 1500, n_obs=8):
+    """MapPoint::ComputeDistinctiveDescriptors inputs: point p holds n_obs (int, or one count per point)
+    descriptor rows, each the point's own random descriptor with every bit flipped with a per-row
+    probability from U(0, 0.2) (observations of one point from different views); one row in eight repeats
+    an earlier row of its point, so equal medians (decided by the lower row) occur.  Returns
+    {"desc": [total, 32] uint8, "begin": [n_points + 1] int32}."""
+    rng = np.random.default_rng(seed)
+    counts = np.full(n_points, int(n_obs), np.int64) if np.isscalar(n_obs) else np.asarray(n_obs, np.int64)
+    assert len(counts) == n_points
+    rows = []
+    for c in counts:
+        c = int(c)
+        base = rng.integers(0, 256, size=32, dtype=np.uint8)
+        mask = rng.random((c, 256)) < rng.uniform(0, 0.2, c)[:, None]
+        d = base[None] ^ np.packbits(mask, axis=1, bitorder="little")
+        for i in range(1, c):
+            if rng.random() < 0.125:
+                d[i] = d[int(rng.integers(0, i))]
+        rows.append(d.astype(np.uint8).reshape(c, 32))
+    desc = np.ascontiguousarray(np.concatenate(rows) if rows else np.zeros((0, 32), np.uint8))
+    return {"desc": desc, "begin": np.concatenate([[0], np.cumsum(counts)]).astype(np.int32)}
