@@ -8,6 +8,8 @@
 #include <cstddef>
 #include <cstdint>
 
+#include "carver.h"
+
 namespace orbamd_host {
 
 // (int2 / int4 as the kernels read them: same size, fields at multiples of 256)
@@ -16,17 +18,6 @@ struct Int2 {
 };
 struct Int4 {
     int x, y, z, w;
-};
-
-// A field takes max(n, 1) elements rounded up to 256 bytes (ba_fill_kernel needs 16-byte aligned segments).
-struct Carver {
-    char* base;
-    size_t off = 0;
-    template <class T>
-    void take(T*& p, size_t n) {
-        p = base ? reinterpret_cast<T*>(base + off) : nullptr;
-        off += (std::max<size_t>(n, 1) * sizeof(T) + 255) / 256 * 256;
-    }
 };
 
 // What the host provides, built in pinned staging and uploaded with a single copy.

@@ -1,5 +1,5 @@
-// ORBmatcher::SearchBySim3 (included by orbp.hip after orbp_fuse.h, whose grid, group scan and packed
-// minimum it builds on).
+// ORBmatcher::SearchBySim3 (included by orbp.hip after orbp_grid.h and orbp_host.h, whose grid, window
+// scan and packed minimum it builds on).
 //
 // Reference: src/ORBmatcher.cc:1090-1277 (LoopClosing::FindLoopInCandidateKFs, LoopClosing.cc:137, th 7.5).
 // The map points of keyframe 1 are taken to camera 1, through S21 = S12.Inverse() to camera 2, projected
@@ -94,10 +94,8 @@ __global__ __launch_bounds__(256) void sim3_project_kernel(Sim3Args a) {
     if (ok) {
         const float* P = src.pose + 12 * (size_t)f;
         const float X0 = src.xw[3 * (size_t)i], X1 = src.xw[3 * (size_t)i + 1], X2 = src.xw[3 * (size_t)i + 2];
-        // WorldToCamera: Rcw * Xw + tcw (cv::Matx: s = 0; s += a(i, k) * b(k) for k = 0..2)
-        const float c0 = ((P[0] * X0 + P[1] * X1) + P[2] * X2) + P[9];
-        const float c1 = ((P[3] * X0 + P[4] * X1) + P[5] * X2) + P[10];
-        const float c2 = ((P[6] * X0 + P[7] * X1) + P[8] * X2) + P[11];
+        const float3 c = pj_world_to_camera(P, X0, X1, X2);   // WorldToCamera
+        const float c0 = c.x, c1 = c.y, c2 = c.z;
         const float* S = a.s12 + 13 * (size_t)f;
         float m[9], t0, t1, t2;   // Sim3::Map: (s * R) * x + t (Sim3.h:40), the matrix scaled elementwise first
         if (d == 0) {
@@ -128,16 +126,10 @@ __global__ __launch_bounds__(256) void sim3_project_kernel(Sim3Args a) {
             ok = u >= bd[0] && u < bd[1] && v >= bd[2] && v < bd[3];   // IsInImage (KeyFrame.cc:496-499)
         }
         if (ok) {
-            // dist3D = (float)cv::norm(Xc) of the mapped camera-frame point (double sum), :1151
-            const double d0 = (double)y0, d1 = (double)y1, d2 = (double)y2;
-            const float dist3D = (float)sqrt((d0 * d0 + d1 * d1) + d2 * d2);
+            const float dist3D = pj_dist3d(y0, y1, y2);   // cv::norm(Xc) of the mapped camera-frame point, :1151
             const float maxD = src.max_min[2 * (size_t)i], minD = src.max_min[2 * (size_t)i + 1];
             ok = !(dist3D < 0.8f * minD || dist3D > 1.2f * maxD);   // :1154, MapPoint.cc:382-392
-            if (ok) {   // PredictScale(dist3D, keyframe) (MapPoint.cc:394-403)
-                const float ratio = maxD / dist3D;
-                const int sc = (int)ceil(log((double)ratio) / (double)a.log_sf);
-                ps = max(0, min(sc, a.n_levels - 1));
-            }
+            if (ok) ps = pj_predict_scale(maxD, dist3D, a.log_sf, a.n_levels);   // PredictScale(dist3D, keyframe)
         }
     }
     src.out_valid[i] = ok ? 1 : 0;
@@ -163,29 +155,16 @@ __global__ __launch_bounds__(256) void sim3_best_kernel(Sim3Args a) {
         const int ps = src.out_level[i];
         const float u = src.out_uv[2 * (size_t)i], v = src.out_uv[2 * (size_t)i + 1];
         const float radius = a.th * a.scale[ps];
-        const float* bd = dst.bounds + 4 * (size_t)f;
-        const float minx = bd[0], miny = bd[2];
-        const float invW = PJ_COLS / (bd[1] - bd[0]), invH = PJ_ROWS / (bd[3] - bd[2]);
-        const int mincx = max((int)floorf(invW * (u - radius - minx)), 0);
-        const int maxcx = min((int)ceilf(invW * (u + radius - minx)), PJ_COLS - 1);
-        const int mincy = max((int)floorf(invH * (v - radius - miny)), 0);
-        const int maxcy = min((int)ceilf(invH * (v + radius - miny)), PJ_ROWS - 1);
-        if (!(mincx >= PJ_COLS || maxcx < 0 || mincy >= PJ_ROWS || maxcy < 0)) {
-            const int32_t* cs = dst.grid_start + (size_t)f * (PJ_CELLS + 1);
-            const uint8_t* d1 = src.mp_desc + 32 * (size_t)i;
-            for (int cx = mincx; cx <= maxcx; cx++) {
-                const int p0 = cs[cx * PJ_ROWS + mincy], p1 = cs[cx * PJ_ROWS + maxcy + 1];
-                for (int p = p0 + lane; p < p1; p += PJ_GW) {
-                    const int k = k0 + dst.grid_idx[k0 + p];
-                    const float kx = dst.kp_xy[2 * (size_t)k], ky = dst.kp_xy[2 * (size_t)k + 1];
-                    if (!(fabsf(kx - u) < radius && fabsf(ky - v) < radius)) continue;
-                    const int scale = dst.kp_oct[k];
-                    if (scale < ps - 1 || scale > ps) continue;
-                    const int dist = pj_hamming(d1, dst.kp_desc + 32 * (size_t)k);
-                    best = min(best, ((uint32_t)dist << PJ_IDX_BITS) | (uint32_t)p);
-                }
-            }
-        }
+        const PjWindow w = pj_window(pj_bounds(dst.bounds + 4 * (size_t)f), u, v, radius);
+        const uint8_t* d1 = src.mp_desc + 32 * (size_t)i;
+        pj_scan_window<PJ_GW>(w, dst.grid_start + (size_t)f * (PJ_CELLS + 1), dst.grid_idx, k0, lane, [&](int p, int idx) {
+            const int k = k0 + idx;
+            if (!pj_in_box(dst.kp_xy[2 * (size_t)k], dst.kp_xy[2 * (size_t)k + 1], u, v, radius)) return;
+            const int scale = dst.kp_oct[k];
+            if (scale < ps - 1 || scale > ps) return;
+            const int dist = pj_hamming(d1, dst.kp_desc + 32 * (size_t)k);
+            best = min(best, ((uint32_t)dist << PJ_IDX_BITS) | (uint32_t)p);
+        });
     }
     best = pj_wave_min<PJ_GW>(best);
     if (lane == 0) {
@@ -208,38 +187,27 @@ __global__ __launch_bounds__(256) void sim3_agree_kernel(Sim3Args a) {
     if (out >= 0) atomicAdd(&a.n_found[f], 1);
 }
 
-// grid_idx / grid_start / pair / out_valid / out_uv / out_level / match of both sides
-static size_t sim3_side_bytes(int n_pairs, int total) {
-    const size_t T = (size_t)std::max(total, 1);
-    return 4 * align_up(T * 4, 256) + align_up((size_t)n_pairs * (PJ_CELLS + 1) * 4, 256) + align_up(T, 256) +
-           align_up(T * 8, 256);
-}
-
-static void sim3_carve(Sim3Args& a, char* ws, int32_t* match1, int32_t* match2) {
-    size_t o = 0;
+// The workspace: one Sim3SideLayout per side; match1 / match2 replace the sides' own match arrays when
+// the caller asks for them.
+static int sim3_workspace(PjScratch& sc, Sim3Args& a, int32_t* match1, int32_t* match2) {
+    orbamd_host::Sim3SideLayout l[2];
+    int rc;
+    if ((rc = sc.workspace([&](Carver& c) {
+            for (int d = 0; d < 2; d++) l[d].carve(c, a.n_pairs, a.s[d].total);
+        })))
+        return rc;
     for (int d = 0; d < 2; d++) {
         Sim3Side& s = a.s[d];
-        const size_t T = (size_t)std::max(s.total, 1);
-        s.grid_idx = (int32_t*)(ws + o);
-        o += align_up(T * 4, 256);
-        s.grid_start = (int32_t*)(ws + o);
-        o += align_up((size_t)a.n_pairs * (PJ_CELLS + 1) * 4, 256);
-        s.pair = (int32_t*)(ws + o);
-        o += align_up(T * 4, 256);
-        s.out_level = (int32_t*)(ws + o);
-        o += align_up(T * 4, 256);
-        s.match = (int32_t*)(ws + o);
-        o += align_up(T * 4, 256);
-        s.out_valid = (uint8_t*)(ws + o);
-        o += align_up(T, 256);
-        s.out_uv = (float*)(ws + o);
-        o += align_up(T * 8, 256);
+        s.grid_idx = l[d].grid_idx; s.grid_start = l[d].grid_start; s.pair = l[d].pair; s.out_level = l[d].out_level;
+        s.match = l[d].match; s.out_valid = l[d].out_valid; s.out_uv = l[d].out_uv;
     }
     if (match1) a.s[0].match = match1;
     if (match2) a.s[1].match = match2;
+    return ORB_OK;
 }
 
 static int launch_search_by_sim3(Sim3Args& a, hipStream_t st) {
+    int rc;
     for (int d = 0; d < 2; d++) {   // side d's grid; its mp_frame pass labels the other side's slots
         PjArgs g;
         std::memset(&g, 0, sizeof(g));
@@ -251,8 +219,7 @@ static int launch_search_by_sim3(Sim3Args& a, hipStream_t st) {
         g.grid_start = a.s[d].grid_start;
         g.mp_begin = a.s[1 - d].kp_begin;
         g.mp_frame = a.s[1 - d].pair;
-        hipLaunchKernelGGL(pj_grid_kernel, dim3(a.n_pairs), dim3(256), 0, st, g);
-        ORB_HIP_TRY(hipGetLastError());
+        if ((rc = launch_grid(g, st))) return rc;
     }
     const int total = a.s[0].total + a.s[1].total;
     hipLaunchKernelGGL(sim3_project_kernel, dim3(std::max((total + 255) / 256, 1)), dim3(256), 0, st, a);
@@ -271,14 +238,12 @@ static int launch_search_by_sim3(Sim3Args& a, hipStream_t st) {
 // Argument checks and the host-side fields shared by both entries.
 static int sim3_common(const orbm_sim3_batch* b, Sim3Args& a) {
     ORB_CHECK_ARG(b, "null argument");
-    ORB_CHECK_ARG(b->n_pairs >= 0 && b->total_kp1 >= 0 && b->total_kp2 >= 0, "negative sizes");
-    ORB_CHECK_ARG(b->n_levels >= 1 && b->n_levels <= PJ_MAX_LEVELS && b->scale_factors, "bad scale pyramid");
+    int rc;
+    if ((rc = pj_check_sizes(b->n_pairs, b->total_kp1, b->total_kp2))) return rc;
     std::memset(&a, 0, sizeof(a));
+    if ((rc = pj_set_pyramid(a, b->n_levels, b->scale_factors, b->th))) return rc;
     a.n_pairs = b->n_pairs;
-    a.n_levels = b->n_levels;
-    for (int l = 0; l < b->n_levels; l++) a.scale[l] = b->scale_factors[l];
     a.log_sf = b->log_scale_factor;
-    a.th = b->th;
     if (b->n_pairs == 0) return ORB_OK;
     ORB_CHECK_ARG(b->kp1_begin && b->kp2_begin && b->bounds1 && b->bounds2 && b->pose1 && b->pose2 && b->camera1 &&
                       b->camera2 && b->s12,
@@ -297,61 +262,22 @@ static int sim3_common(const orbm_sim3_batch* b, Sim3Args& a) {
     return ORB_OK;
 }
 
-// kp1_begin / kp2_begin of a host batch
-static int sim3_check_offsets(const orbm_sim3_batch* b) {
-    const int F = b->n_pairs;
-    ORB_CHECK_ARG(b->kp1_begin[0] == 0 && b->kp2_begin[0] == 0 && b->kp1_begin[F] == b->total_kp1 &&
-                      b->kp2_begin[F] == b->total_kp2,
-                  "kp1_begin / kp2_begin must start at 0 and end at total_kp1 / total_kp2");
-    for (int f = 0; f < F; f++) {
-        ORB_CHECK_ARG(b->kp1_begin[f + 1] >= b->kp1_begin[f] && b->kp2_begin[f + 1] >= b->kp2_begin[f],
-                      "offsets must be non-decreasing");
-        ORB_CHECK_ARG(b->kp1_begin[f + 1] - b->kp1_begin[f] <= PJ_MAXKP && b->kp2_begin[f + 1] - b->kp2_begin[f] <= PJ_MAXKP,
-                      "keyframe has more than ORBM_PROJ_MAX_KP keypoints");
-    }
-    return ORB_OK;
-}
-
-// A host batch copied into `io`: `d` = the batch with device pointers (scale_factors stays host), d_extra =
-// extra_bytes of output room behind it.
-static int sim3_upload(const orbm_sim3_batch* b, DevBuf& io, size_t extra_bytes, orbm_sim3_batch& d, char*& d_extra) {
-    const int F = b->n_pairs;
-    size_t off = 0;
-    auto take = [&](size_t bytes) { const size_t o = off; off += align_up(std::max<size_t>(bytes, 1), 256); return o; };
-    struct Item { const void* src; size_t bytes; size_t o; };
-    const size_t K1 = (size_t)b->total_kp1, K2 = (size_t)b->total_kp2;
-    Item it[] = {
-        {b->kp1_begin, (size_t)(F + 1) * 4, 0}, {b->kp2_begin, (size_t)(F + 1) * 4, 0},
-        {b->kp1_xy, K1 * 8, 0}, {b->kp1_octave, K1 * 4, 0}, {b->kp1_desc, K1 * 32, 0},
-        {b->kp2_xy, K2 * 8, 0}, {b->kp2_octave, K2 * 4, 0}, {b->kp2_desc, K2 * 32, 0},
-        {b->bounds1, (size_t)F * 16, 0}, {b->pose1, (size_t)F * 48, 0}, {b->camera1, (size_t)F * 16, 0},
-        {b->bounds2, (size_t)F * 16, 0}, {b->pose2, (size_t)F * 48, 0}, {b->camera2, (size_t)F * 16, 0},
-        {b->mp1_valid, K1, 0}, {b->mp1_xw, K1 * 12, 0}, {b->mp1_max_min, K1 * 8, 0}, {b->mp1_desc, K1 * 32, 0},
-        {b->mp2_valid, K2, 0}, {b->mp2_xw, K2 * 12, 0}, {b->mp2_max_min, K2 * 8, 0}, {b->mp2_desc, K2 * 32, 0},
-        {b->s12, (size_t)F * 52, 0},
-    };
-    for (Item& i : it) i.o = take(i.bytes);
-    const size_t o_ex = take(extra_bytes);
-    int rc;
-    if ((rc = io.reserve(off))) return rc;
-    char* p = io.as<char>();
-    for (const Item& i : it)
-        if (i.bytes && i.src) ORB_HIP_TRY(hipMemcpy(p + i.o, i.src, i.bytes, hipMemcpyHostToDevice));
+// A host batch copied into the scratch: `d` = the batch with device pointers (scale_factors stays host),
+// `out` = the entry's output arrays behind it.
+static int sim3_upload(PjScratch& s, const orbm_sim3_batch* b, orbm_sim3_batch& d, std::initializer_list<PjOut> out) {
+    const size_t F = b->n_pairs, K1 = b->total_kp1, K2 = b->total_kp2;
     d = *b;
-    int n = 0;
-    auto at = [&]() { return (const void*)(p + it[n++].o); };
-    d.kp1_begin = (const int32_t*)at(); d.kp2_begin = (const int32_t*)at();
-    d.kp1_xy = (const float*)at(); d.kp1_octave = (const int32_t*)at(); d.kp1_desc = (const uint8_t*)at();
-    d.kp2_xy = (const float*)at(); d.kp2_octave = (const int32_t*)at(); d.kp2_desc = (const uint8_t*)at();
-    d.bounds1 = (const float*)at(); d.pose1 = (const float*)at(); d.camera1 = (const float*)at();
-    d.bounds2 = (const float*)at(); d.pose2 = (const float*)at(); d.camera2 = (const float*)at();
-    d.mp1_valid = (const uint8_t*)at(); d.mp1_xw = (const float*)at(); d.mp1_max_min = (const float*)at();
-    d.mp1_desc = (const uint8_t*)at();
-    d.mp2_valid = (const uint8_t*)at(); d.mp2_xw = (const float*)at(); d.mp2_max_min = (const float*)at();
-    d.mp2_desc = (const uint8_t*)at();
-    d.s12 = (const float*)at();
-    d_extra = p + o_ex;
-    return ORB_OK;
+    return s.upload({{b->kp1_begin, F + 1, d.kp1_begin}, {b->kp2_begin, F + 1, d.kp2_begin},
+                     {b->kp1_xy, 2 * K1, d.kp1_xy}, {b->kp1_octave, K1, d.kp1_octave}, {b->kp1_desc, 32 * K1, d.kp1_desc},
+                     {b->kp2_xy, 2 * K2, d.kp2_xy}, {b->kp2_octave, K2, d.kp2_octave}, {b->kp2_desc, 32 * K2, d.kp2_desc},
+                     {b->bounds1, 4 * F, d.bounds1}, {b->pose1, 12 * F, d.pose1}, {b->camera1, 4 * F, d.camera1},
+                     {b->bounds2, 4 * F, d.bounds2}, {b->pose2, 12 * F, d.pose2}, {b->camera2, 4 * F, d.camera2},
+                     {b->mp1_valid, K1, d.mp1_valid}, {b->mp1_xw, 3 * K1, d.mp1_xw}, {b->mp1_max_min, 2 * K1, d.mp1_max_min},
+                     {b->mp1_desc, 32 * K1, d.mp1_desc},
+                     {b->mp2_valid, K2, d.mp2_valid}, {b->mp2_xw, 3 * K2, d.mp2_xw}, {b->mp2_max_min, 2 * K2, d.mp2_max_min},
+                     {b->mp2_desc, 32 * K2, d.mp2_desc},
+                     {b->s12, 13 * F, d.s12}},
+                    out);
 }
 
 }  // namespace orbamd

@@ -68,7 +68,25 @@ def test_search_by_projection_device_matches_host():
     assert torch.equal(dk, dk2) and torch.equal(dn, dn2)
 
 
-def test_search_by_projection_device_oversized_frame():
+def one_frame(b, f, other="mp_begin"):
+    """Frame f of a batch as a batch of its own: arrays sliced by their first dimension (keypoint rows, point
+    rows, one row per frame).  The three lengths and n_frames + 1 have to differ."""
+    kb, ob = b["kp_begin"], b[other]
+    K, N, F = int(kb[-1]), int(ob[-1]), len(kb) - 1
+    assert len({K, N, F, F + 1}) == 4
+    out = {}
+    for k, v in b.items():
+        if not isinstance(v, np.ndarray) or k in ("scale_factors", "inv_sigma2"):
+            out[k] = v
+        elif k in ("kp_begin", other):
+            out[k] = np.array([0, v[f + 1] - v[f]], np.int32)
+        else:
+            lo, hi = {K: (kb[f], kb[f + 1]), N: (ob[f], ob[f + 1]), F: (f, f + 1)}[len(v)]
+            out[k] = v[lo:hi]
+    return out
+
+
+def test_search_by_projection_device_oversized_frame(oracle):
     import torch
     b = make_proj_batch(10, n_frames=2, n_kp=[8193, 300], n_mp=[10, 200])
     dk, dn = search_by_projection_device(_to_dev(b))
@@ -76,3 +94,6 @@ def test_search_by_projection_device_oversized_frame():
     n = dn.cpu().numpy()
     assert n[0] == -1 and n[1] >= 0
     assert (dk.cpu().numpy()[:8193] == -1).all()
+    # the frame within the limit is unaffected
+    ek, en = oracle.search_by_projection(one_frame(b, 1))
+    assert en[0] > 0 and n[1] == en[0] and np.array_equal(dk.cpu().numpy()[8193:8493], ek)

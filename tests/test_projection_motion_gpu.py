@@ -88,7 +88,7 @@ def test_motion_projection_bad_octave_is_skipped(oracle):
     assert np.array_equal(nm.cpu().numpy(), exp_n)
 
 
-def test_motion_projection_over_limit_frame_reports_minus_one():
+def test_motion_projection_over_limit_frame_reports_minus_one(oracle):
     """A frame above the device keypoint limit gets n_matches = -1 and kp_match = -1 on every keypoint
     (initialised, never garbage), the other frames are unaffected."""
     import torch
@@ -108,3 +108,6 @@ def test_motion_projection_over_limit_frame_reports_minus_one():
     torch.cuda.synchronize()
     assert int(nm[0]) == -1
     assert bool((km[:9000] == -1).all())
+    from test_projection_gpu import one_frame
+    ek, en = oracle.search_by_projection_motion(one_frame(m, 1))
+    assert en[0] > 0 and int(nm[1]) == en[0] and np.array_equal(km.cpu().numpy()[9000:K], ek)

@@ -48,8 +48,12 @@ def test_reloc_heavy_sharing_no_claims(oracle):
     _check(oracle, b)
 
 
-def test_reloc_over_limit_frame():
+def test_reloc_over_limit_frame(oracle):
     b = make_reloc_batch(88, n_frames=2, n_kp=[9000, 500], n_mp=[100, 100])
     import torch
     km, nm = _device(b, kp_match=torch.full((9500,), 12345, dtype=torch.int32, device="cuda"))
     assert nm[0] == -1 and (km[:9000] == -1).all()
+    # the frame within the limit is unaffected
+    from test_projection_gpu import one_frame
+    ek, en = oracle.search_by_projection_reloc(one_frame(b, 1))
+    assert en[0] > 0 and nm[1] == en[0] and np.array_equal(km[9000:], ek)

@@ -47,3 +47,19 @@ def test_sim3_without_entry_claims():
     b = _batch(6)
     b["kp_claimed"] = None
     _check(b)
+
+
+def test_sim3_over_limit_item():
+    """A keyframe above the device keypoint limit gets n_matches = -1 and kp_match = -1 on every keypoint
+    (initialised, never garbage); the item within the limit is unaffected."""
+    import torch
+    from test_projection_gpu import one_frame
+    b = make_fuse_batch(9, n_items=2, n_kp=[8193, 300], n_mp=[40, 200], th=10.0, chi2_gate=False, dup_frac=0.5,
+                        claimed_frac=0.1)
+    km, nm = search_by_projection_sim3_device(to_device(b), kp_match=torch.full((8493,), 12345, dtype=torch.int32,
+                                                                                device="cuda"))
+    torch.cuda.synchronize()
+    km, nm = km.cpu().numpy(), nm.cpu().numpy()
+    assert nm[0] == -1 and (km[:8193] == -1).all()
+    exp, en = fuse_ref.search_by_projection_sim3(one_frame(b, 1))
+    assert en[0] > 0 and nm[1] == en[0] and np.array_equal(km[8193:8493], exp)
