@@ -777,6 +777,79 @@ int orbba_pose_optimization(const orbba_pose_batch* in, orbba_pose_result* out, 
  * stream).  One workgroup per frame. */
 int orbba_pose_optimization_device(const orbba_pose_batch* in, orbba_pose_result* out, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * int Optimizer::OptimizeSim3(KeyFrame* keyframe1, KeyFrame* keyframe2, std::vector<MapPoint*>& matches1,
+ * Sim3& S12, float maxChi2, bool fixScale) (include/Optimizer.h, src/Optimizer.cc:944-1100;
+ * LoopClosing::FindLoopInCandidateKFs, LoopClosing.cc:139, maxChi2 10), batched over (keyframe1,
+ * keyframe2, S12) pairs in orbm_sim3_batch's slot layout, so orbm_search_by_sim3_device's match12 feeds
+ * straight in.  fp64 throughout, one launch per batch.
+ * Vertex: VertexSim3Expmap with the estimate g2o::Sim3(R12, t12, (float)s) widened to double, the rotation
+ * through Quaterniond(R) without renormalisation (Optimizer.cc:183-188, sim3.h:64-67), _fix_scale =
+ * fix_scale, both keyframes' intrinsics widened from float.
+ * Correspondences: slot i of keyframe 1, ascending, is kept iff mp1_valid[i] && match12[i] >= 0 &&
+ * mp2_valid[match12[i]] (:993-1001; i2 = match12[i] stands for GetIndexInKeyFrame(keyframe2)).  Its two
+ * fixed points are Xc1 = R1w * Xw1 + t1w and Xc2 = R2w * Xw2 + t2w in float, then widened (:1006-1012).
+ * Edges (:1016-1038; types_seven_dof_expmap.h:138-145, :160-167; sim3.h:144-146, :233-236):
+ *   e12 = kp1_xy[i]  - cam_map1(project(S.map(Xc2))),            Omega = inv_level_sigma2[kp1_octave[i]]  * I
+ *   e21 = kp2_xy[i2] - cam_map2(project(S.inverse().map(Xc1))),  Omega = inv_level_sigma2[kp2_octave[i2]] * I
+ * both with a Huber kernel of delta = sqrt((double)max_chi2) that is kept for the second round.
+ * Jacobian: the edges have no linearizeOplus, so it is g2o's numeric one (base_binary_edge.hpp:143-200):
+ * column d = (e(+delta) - e(-delta)) * (1 / (2 delta)), delta = 1e-9, each perturbed estimate being
+ * Sim3(update) * estimate (oplusImpl, types_seven_dof_expmap.h:60-69; Sim3(Vector7d), sim3.h:70-142, with
+ * its four eps = 1e-5 branches).  With fix_scale update[6] is zeroed, so column 6 is exactly 0.
+ * Solver: Levenberg-Marquardt as in orbba_pose_optimization (optimization_algorithm_levenberg.cpp:61-189:
+ * lambda0 = 1e-5 max diag, at most 10 trials, rho with the 1e-3 term, the nBad stop), robust weighting of
+ * base_binary_edge.hpp:54-120 / robust_kernel_impl.cpp:65-91, and an unpivoted dense LDL^T of the 7 x 7
+ * (linear_solver_dense.h:65-115; a negative pivot fails the solve).
+ * Schedule (:1046-1099): optimize(5); every correspondence with e12.chi2() > max_chi2 || e21.chi2() >
+ * max_chi2 loses its match (match12[i] = -1), its two edges, and counts in nbad, chi2() being e' Omega e of
+ * the last computed error (after a rejected last trial that is the rejected trial's error; nothing is
+ * recomputed).  If ncorrespondences - nbad < 10 the call returns 0 with S12 unchanged and the matches
+ * already removed stay removed.  Otherwise optimize(nbad > 0 ? 10 : 5) on the survivors, the same test
+ * removes matches and counts n_inliers, and S12 = FromG2OSim3(estimate). */
+#define ORBBA_SIM3_MAX_CORR ORBM_PROJ_MAX_KP   /* correspondences per pair */
+
+typedef struct orbba_sim3_batch {
+    int32_t        n_pairs, total_kp1, total_kp2;
+    const int32_t* kp1_begin;    /* n_pairs + 1 */
+    const int32_t* kp2_begin;    /* n_pairs + 1 */
+    const float*   kp1_xy;       /* keyframe 1 keypointsUn pt, total_kp1 x 2 */
+    const int32_t* kp1_octave;
+    const float*   kp2_xy;       /* keyframe 2, total_kp2 rows */
+    const int32_t* kp2_octave;
+    const float*   pose1;        /* n_pairs x 12: Rcw (row-major 3x3) then tcw */
+    const float*   camera1;      /* n_pairs x 4: fx, fy, cx, cy */
+    const float*   pose2;
+    const float*   camera2;
+    const uint8_t* mp1_valid;    /* total_kp1: mappoints1[i] && !mappoints1[i]->isBad() */
+    const float*   mp1_xw;       /* total_kp1 x 3 */
+    const uint8_t* mp2_valid;    /* total_kp2: the map point of slot i2 exists and is not bad */
+    const float*   mp2_xw;       /* total_kp2 x 3 */
+    const float*   s12;          /* n_pairs x 13: R12 (row-major 3x3), t12, s */
+    const int32_t* match12;      /* total_kp1: keyframe-2-relative index of matches1[i] or -1 */
+    int32_t        n_levels;
+    const float*   inv_level_sigma2; /* host, n_levels (pyramid.invSigmaSq) */
+    float          max_chi2;
+    int32_t        fix_scale;    /* per batch */
+} orbba_sim3_batch;
+
+typedef struct orbba_sim3_result {
+    float*   s12;        /* n_pairs x 13: S12 on return; the input row when the pair returns 0 */
+    double*  s12_g2o;    /* n_pairs x 8: q (x, y, z, w), t, s of the vertex estimate when the call returned;
+                          * may be NULL */
+    int32_t* match12;    /* total_kp1: the thinned matches; may alias the input */
+    int32_t* n_inliers;  /* n_pairs: the return value; -1 from the device entry for a pair with more than
+                          * ORBBA_SIM3_MAX_CORR correspondences (its s12 and match12 are the input's) */
+    int32_t* iterations; /* n_pairs x 2: LM iterations of the two optimize() calls; may be NULL */
+} orbba_sim3_result;
+
+/* Host entry: every pointer is host memory, synchronous; offsets, octaves and the range of match12 are
+ * validated; a pair with more than ORBBA_SIM3_MAX_CORR correspondences is refused. */
+int orbba_optimize_sim3(const orbba_sim3_batch* in, orbba_sim3_result* out, int device);
+/* Device entry: every array in HBM except inv_level_sigma2; enqueue only on `stream`.  One wavefront per
+ * pair. */
+int orbba_optimize_sim3_device(const orbba_sim3_batch* in, orbba_sim3_result* out, void* stream);
+
 const char* orb_last_error(void);
 int orb_device_count(void);
 

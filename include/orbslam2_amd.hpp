@@ -6,6 +6,7 @@
 //   ORB_SLAM2_AMD::ORBmatcher     <- ORB_SLAM2::ORBmatcher Hamming kernels (include/ORBmatcher.h)
 //   ORB_SLAM2_AMD::LocalBundleAdjustment <- Optimizer::LocalBundleAdjustment (include/Optimizer.h:47)
 //   ORB_SLAM2_AMD::PoseOptimization      <- Optimizer::PoseOptimization (include/Optimizer.h:49)
+//   ORB_SLAM2_AMD::Optimizer::OptimizeSim3 <- Optimizer::OptimizeSim3 (src/Optimizer.cc:944-1100)
 //   ORB_SLAM2_AMD::SearchByProjection    <- ORBmatcher::SearchByProjection(Frame&, vector<MapPoint*>, th)
 //   ORB_SLAM2_AMD::ORBVocabulary         <- DBoW2 ORBVocabulary (include/ORBVocabulary.h) transform
 // Plain-type overloads are always available; when OpenCV is on the include path the
@@ -464,6 +465,33 @@ inline int SearchBySim3(const orbm_sim3_batch& b, std::vector<int32_t>& match12,
     match12.resize(b.total_kp1);
     return nf;
 }
+
+// int Optimizer::OptimizeSim3(KeyFrame*, KeyFrame*, std::vector<MapPoint*>& matches1, Sim3& S12, float maxChi2,
+// bool fixScale) (src/Optimizer.cc:944-1100; LoopClosing.cc:139), batched over (keyframe1, keyframe2, S12)
+// pairs on HBM arrays in SearchBySim3's slot layout (orbba_sim3_batch: match12 is SearchBySim3Batch's output,
+// mp1_valid / mp2_valid = the slot has a map point that is not bad).  Enqueue only, one launch: r.s12 = S12 on
+// return, r.match12 (may alias b.match12) = the thinned matches, r.n_inliers = the return values.
+struct Optimizer {
+    static void OptimizeSim3Batch(const orbba_sim3_batch& b, orbba_sim3_result& r, void* stream = nullptr) {
+        check(orbba_optimize_sim3_device(&b, &r, stream), "orbba_optimize_sim3_device");
+    }
+    // The same for one pair on host arrays: match12 (total_kp1, in / out) and s12 (13 floats R, t, s, in / out);
+    // returns the inlier count.
+    static int OptimizeSim3(orbba_sim3_batch b, std::vector<int32_t>& match12, float* s12, int device = 0) {
+        if (b.n_pairs != 1) throw std::invalid_argument("OptimizeSim3: one pair per call (use the batch form)");
+        if (match12.size() < static_cast<size_t>(b.total_kp1)) throw std::invalid_argument("OptimizeSim3: match12 is short");
+        b.match12 = match12.data();
+        b.s12 = s12;
+        float out_s12[13];
+        int32_t n = 0;
+        std::vector<int32_t> thinned(std::max(b.total_kp1, 1), -1);
+        orbba_sim3_result r = {out_s12, nullptr, thinned.data(), &n, nullptr};
+        check(orbba_optimize_sim3(&b, &r, device), "orbba_optimize_sim3");
+        std::copy(thinned.begin(), thinned.begin() + b.total_kp1, match12.begin());
+        std::copy(out_s12, out_s12 + 13, s12);
+        return n;
+    }
+};
 
 // void MapPoint::ComputeDistinctiveDescriptors() (src/MapPoint.cc:257-320), batched over map points on HBM
 // arrays: point p holds the rows [begin[p], begin[p + 1]) of d_desc.  Enqueue only; best[p] = the winning

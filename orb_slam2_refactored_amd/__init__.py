@@ -5,6 +5,7 @@ Host mirrors of the reference's interfaces (tiantianxuabc/ORB_SLAM2_Refactored):
   ORBmatcher          <- include/ORBmatcher.h (Hamming kernels)
   Optimizer.LocalBundleAdjustment <- include/Optimizer.h:47
   Optimizer.PoseOptimization      <- include/Optimizer.h:49
+  Optimizer.OptimizeSim3          <- src/Optimizer.cc:944-1100
 All compute runs in liborbslam2_amd.so (HIP kernels behind include/orbslam2_amd.h).
 """
 from .extractor import ORBextractor, KP_DTYPE

@@ -144,6 +144,23 @@ class PoseResult(C.Structure):
     _fields_ = [("pose_R", C.c_void_p), ("pose_t", C.c_void_p), ("n_inliers", C.c_void_p), ("outlier", C.c_void_p)]
 
 
+class OptSim3Batch(C.Structure):
+    """orbba_sim3_batch (include/orbslam2_amd.h)."""
+    _fields_ = [("n_pairs", C.c_int32), ("total_kp1", C.c_int32), ("total_kp2", C.c_int32),
+                ("kp1_begin", C.c_void_p), ("kp2_begin", C.c_void_p),
+                ("kp1_xy", C.c_void_p), ("kp1_octave", C.c_void_p), ("kp2_xy", C.c_void_p), ("kp2_octave", C.c_void_p),
+                ("pose1", C.c_void_p), ("camera1", C.c_void_p), ("pose2", C.c_void_p), ("camera2", C.c_void_p),
+                ("mp1_valid", C.c_void_p), ("mp1_xw", C.c_void_p), ("mp2_valid", C.c_void_p), ("mp2_xw", C.c_void_p),
+                ("s12", C.c_void_p), ("match12", C.c_void_p), ("n_levels", C.c_int32),
+                ("inv_level_sigma2", C.c_void_p), ("max_chi2", C.c_float), ("fix_scale", C.c_int32)]
+
+
+class OptSim3Result(C.Structure):
+    """orbba_sim3_result (include/orbslam2_amd.h)."""
+    _fields_ = [("s12", C.c_void_p), ("s12_g2o", C.c_void_p), ("match12", C.c_void_p), ("n_inliers", C.c_void_p),
+                ("iterations", C.c_void_p)]
+
+
 # cv::KeyPoint layout (28 bytes)
 KP_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("size", "<f4"), ("angle", "<f4"),
                      ("response", "<f4"), ("octave", "<i4"), ("class_id", "<i4")])
@@ -211,6 +228,8 @@ SIGNATURES = {
     "orbba_local_ba": (C.c_int, [C.POINTER(BAProblem), C.POINTER(BAResult), VP, C.c_int]),
     "orbba_pose_optimization": (C.c_int, [C.POINTER(PoseBatch), C.POINTER(PoseResult), C.c_int]),
     "orbba_pose_optimization_device": (C.c_int, [C.POINTER(PoseBatch), C.POINTER(PoseResult), VP]),
+    "orbba_optimize_sim3": (C.c_int, [C.POINTER(OptSim3Batch), C.POINTER(OptSim3Result), C.c_int]),
+    "orbba_optimize_sim3_device": (C.c_int, [C.POINTER(OptSim3Batch), C.POINTER(OptSim3Result), VP]),
     "orbx_pack_descriptors": (C.c_int, [VP, C.c_int, VP, VP, C.c_int, VP, C.c_int, VP]),
     "orbx_profile_enable": (C.c_int, [VP, C.c_int]),
     "orbx_profile_read": (C.c_int, [VP, VP, VP]),

@@ -6,6 +6,8 @@
 // src/ORBmatcher.cc:249-309 (CheckOrientation).
 #pragma once
 
+#include "world_to_camera.h"
+
 namespace orbamd {
 
 using orbamd_host::PJ_CELLS;
@@ -207,11 +209,7 @@ __device__ __forceinline__ uint32_t pjm_keep_bins(const int* hist, int* kept) {
 
 // ---------------------------------------------------------------- projection pieces
 // P = a pose, 12 floats: Rcw (row-major) then tcw.
-// Rcw * Xw + tcw (cv::Matx: s = 0; s += a(i, k) * b(k) for k = 0..2)
-__device__ __forceinline__ float3 pj_world_to_camera(const float* P, float X0, float X1, float X2) {
-    return make_float3(((P[0] * X0 + P[1] * X1) + P[2] * X2) + P[9], ((P[3] * X0 + P[4] * X1) + P[5] * X2) + P[10],
-                       ((P[6] * X0 + P[7] * X1) + P[8] * X2) + P[11]);
-}
+// (pj_world_to_camera: world_to_camera.h)
 
 // Ow = -Rcw^T * tcw (CameraPose::Invt)
 __device__ __forceinline__ float3 pj_camera_centre(const float* P) {

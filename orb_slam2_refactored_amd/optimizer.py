@@ -1,4 +1,4 @@
-"""Optimizer::LocalBundleAdjustment / PoseOptimization mirrors (include/Optimizer.h:47-49) over the
+"""Optimizer::LocalBundleAdjustment / PoseOptimization / OptimizeSim3 mirrors (include/Optimizer.h:47-56) over the
 gfx950 C-ABI.
 
 The reference's graph gathering (local KFs by covisibility, local MPs, fixed KFs; Optimizer.cc:493-537)
@@ -10,7 +10,8 @@ import ctypes as C
 
 import numpy as np
 
-from ._lib import BAProblem, BAResult, PoseBatch, PoseResult, check, lib, ptr, stream_ptr, tptr
+from ._lib import (BAProblem, BAResult, OptSim3Batch, OptSim3Result, PoseBatch, PoseResult, check, lib, ptr, stream_ptr,
+                   tptr)
 
 
 def _need(arrays: dict, counts: dict, what: str):
@@ -116,4 +117,89 @@ def pose_optimization_device(batch: dict, out: dict | None = None, stream=None) 
     res = PoseResult(tptr(out["pose_R"]), tptr(out["pose_t"]), tptr(out["n_inliers"]), tptr(out["outlier"]))
     check(lib().orbba_pose_optimization_device(C.byref(pb), C.byref(res), stream_ptr(stream)),
           "orbba_pose_optimization_device")
+    return out
+
+
+# orbba_sim3_batch arrays in struct order: name -> (dtype, rows, row width); F pairs, K1 / K2 keypoint slots
+_OPTSIM3_KEYS = (("kp1_begin", np.int32, "F1", 1), ("kp2_begin", np.int32, "F1", 1),
+                 ("kp1_xy", np.float32, "K1", 2), ("kp1_octave", np.int32, "K1", 1),
+                 ("kp2_xy", np.float32, "K2", 2), ("kp2_octave", np.int32, "K2", 1),
+                 ("pose1", np.float32, "F", 12), ("camera1", np.float32, "F", 4),
+                 ("pose2", np.float32, "F", 12), ("camera2", np.float32, "F", 4),
+                 ("mp1_valid", np.uint8, "K1", 1), ("mp1_xw", np.float32, "K1", 3),
+                 ("mp2_valid", np.uint8, "K2", 1), ("mp2_xw", np.float32, "K2", 3),
+                 ("s12", np.float32, "F", 13), ("match12", np.int32, "K1", 1))
+
+
+def _optsim3_struct(batch, conv, F, K1, K2, what):
+    for k, _, _, _ in _OPTSIM3_KEYS:
+        if batch.get(k) is None:
+            raise ValueError(f"{what}: {k} is required")
+    dims = {"F": F, "F1": F + 1, "K1": K1, "K2": K2}
+    _need(batch, {k: dims[rows] * width for k, _, rows, width in _OPTSIM3_KEYS}, what)
+    isig = np.ascontiguousarray(batch["inv_level_sigma2"], np.float32)
+    sb = OptSim3Batch(F, K1, K2, *[conv(batch[k], dt) for k, dt, _, _ in _OPTSIM3_KEYS], len(isig), ptr(isig),
+                      float(batch["max_chi2"]), int(bool(batch["fix_scale"])))
+    return sb, isig
+
+
+def OptimizeSim3(batch: dict, device: int = 0) -> dict:
+    """int Optimizer::OptimizeSim3(keyframe1, keyframe2, matches1, S12, maxChi2, fixScale)
+    (src/Optimizer.cc:944-1100; LoopClosing.cc:139) batched over (keyframe1, keyframe2, S12) pairs on host
+    arrays in the orbba_sim3_batch layout (include/orbslam2_amd.h): SearchBySim3's slot arrays, its match12,
+    inv_level_sigma2, max_chi2 and fix_scale.  Returns s12 (F, 13) = S12 on return (the input row when the
+    pair returns 0), s12_g2o (F, 8) = q xyzw, t, s of the vertex estimate, match12 (total_kp1) = the thinned
+    matches, n_inliers (F) = the return value and iterations (F, 2)."""
+    for k in ("kp1_begin", "kp2_begin"):
+        if batch.get(k) is None:
+            raise ValueError(f"OptimizeSim3: {k} is required")
+    F = len(batch["kp1_begin"]) - 1
+    K1, K2 = int(batch["kp1_begin"][-1]), int(batch["kp2_begin"][-1])
+    keep = []
+
+    def k(a, dt):
+        a = np.ascontiguousarray(a, dt)
+        keep.append(a)
+        return ptr(a)
+
+    sb, _isig = _optsim3_struct(batch, k, F, K1, K2, "OptimizeSim3")
+    out = dict(s12=np.zeros((F, 13), np.float32), s12_g2o=np.zeros((F, 8)), match12=np.zeros(max(K1, 1), np.int32),
+               n_inliers=np.zeros(F, np.int32), iterations=np.zeros((F, 2), np.int32))
+    res = OptSim3Result(ptr(out["s12"]), ptr(out["s12_g2o"]), ptr(out["match12"]), ptr(out["n_inliers"]),
+                        ptr(out["iterations"]))
+    check(lib().orbba_optimize_sim3(C.byref(sb), C.byref(res), int(device)), "orbba_optimize_sim3")
+    out["match12"] = out["match12"][:K1]
+    return out
+
+
+def optimize_sim3_device(batch: dict, out: dict | None = None, stream=None) -> dict:
+    """Device form of OptimizeSim3: GPU tensors for the orbba_sim3_batch arrays (the dtypes of
+    search_by_sim3_device, whose match12 output feeds in as it is), host values for inv_level_sigma2,
+    max_chi2 and fix_scale; enqueues one launch on `stream` (default: torch's current stream).  `out` may
+    hold the output tensors s12, s12_g2o, match12, n_inliers, iterations; out["match12"] may be
+    batch["match12"], which is then thinned in place.  n_inliers[p] = -1 for a pair with more than
+    ORBBA_SIM3_MAX_CORR correspondences."""
+    import torch
+    for k in ("kp1_begin", "kp1_xy", "kp2_xy"):
+        if batch.get(k) is None:
+            raise ValueError(f"optimize_sim3_device: {k} is required")
+    kb = batch["kp1_begin"]
+    F = kb.numel() - 1
+    K1, K2 = int(batch["kp1_xy"].shape[0]), int(batch["kp2_xy"].shape[0])
+    for name, dt, _, _ in _OPTSIM3_KEYS:
+        t = batch.get(name)
+        if t is not None and (t.dtype != getattr(torch, np.dtype(dt).name) or not t.is_contiguous() or not t.is_cuda):
+            raise ValueError(f"optimize_sim3_device: {name} must be a contiguous {np.dtype(dt).name} GPU tensor")
+    sb, _isig = _optsim3_struct(batch, lambda t, dt: tptr(t), F, K1, K2, "optimize_sim3_device")
+    out = dict(out or {})
+    new = lambda shape, dt: torch.empty(shape, dtype=dt, device=kb.device)   # noqa: E731
+    out.setdefault("s12", new((F, 13), torch.float32))
+    out.setdefault("s12_g2o", new((F, 8), torch.float64))
+    out.setdefault("match12", new(max(K1, 1), torch.int32))
+    out.setdefault("n_inliers", new(max(F, 1), torch.int32))
+    out.setdefault("iterations", new((max(F, 1), 2), torch.int32))
+    _need(out, {"s12": 13 * F, "s12_g2o": 8 * F, "match12": K1, "n_inliers": F, "iterations": 2 * F},
+          "optimize_sim3_device")
+    res = OptSim3Result(*[tptr(out[k]) for k in ("s12", "s12_g2o", "match12", "n_inliers", "iterations")])
+    check(lib().orbba_optimize_sim3_device(C.byref(sb), C.byref(res), stream_ptr(stream)), "orbba_optimize_sim3_device")
     return out

@@ -971,3 +971,107 @@ def make_observation_sets(seed: int = 0, n_points: int = 1500, n_obs=8):
         rows.append(d.astype(np.uint8).reshape(c, 32))
     desc = np.ascontiguousarray(np.concatenate(rows) if rows else np.zeros((0, 32), np.uint8))
     return {"desc": desc, "begin": np.concatenate([[0], np.cumsum(counts)]).astype(np.int32)}
+
+
+def make_optsim3_batch(seed: int = 0, n_corr=(150,), n_outliers=0, noise: bool = True, rot_deg: float = 1.0,
+                       trans: float = 0.03, dscale: float = 0.02, extras: int = 3, max_chi2: float = 10.0,
+                       fix_scale: bool = False, cam=KITTI):
+    """A batch of Optimizer::OptimizeSim3 problems in the orbba_sim3_batch layout (loop candidates).
+
+    Pair p has n_corr[p] correspondences.  The ground truth S12 (rotation N(0, 3 deg), |t| ~ 0.3, s in
+    U(0.8, 1.25), or 1 with fix_scale) takes camera-2 coordinates to camera-1 coordinates.  Points are
+    back-projected from uniform pixels of camera 1 at depth U(4, 40) and kept when they also lie in front of
+    camera 2 (depth > 1); both keyframes have random world poses, and the world positions, measurements and
+    intrinsics are rounded to float32, as the reference stores them.  Octaves U{0..7}, pixel noise
+    N(0, 1.2^oct) per axis on both measurements (`noise`), inv_level_sigma2 = 1 / 1.2^(2 level) in float.
+    n_outliers (int or per-pair list): that many correspondences of the pair get +-U(15, 40) px on both
+    axes of the keyframe-2 measurement, as the C4 generator's gross outliers.  The start s12 is the truth
+    perturbed by N(0, rot_deg) rotation, N(0, trans) translation and a factor 1 + N(0, dscale) (none with
+    fix_scale).  Keyframe 2's slots are a random permutation, and each keyframe carries `extras` slots of
+    each kind the keep test must drop: no map point in keyframe 1, no match, a match whose map point in
+    keyframe 2 is bad.  Returns the batch plus gt_s12 (F, 13), outlier (total_kp1, bool) and n_corr."""
+    rng = np.random.default_rng(seed)
+    counts = [int(n) for n in np.atleast_1d(n_corr)]
+    F = len(counts)
+    n_out = [int(n_outliers)] * F if np.isscalar(n_outliers) else [int(n) for n in n_outliers]
+    camv = np.array([cam[k] for k in ("fx", "fy", "cx", "cy")], np.float32)
+    fx, fy, cx, cy = camv.astype(np.float64)
+    f32 = lambda a: np.asarray(a, np.float64).astype(np.float32)   # noqa: E731
+    kp1_begin, kp2_begin = [0], [0]
+    col = {k: [] for k in ("kp1_xy", "kp1_octave", "kp2_xy", "kp2_octave", "mp1_valid", "mp1_xw", "mp2_valid", "mp2_xw",
+                           "match12", "outlier")}
+    pose1, pose2, s12, gt = [], [], [], []
+    for p, n in enumerate(counts):
+        R12 = _small_rot(rng, 3.0)
+        t12 = rng.normal(0, 0.2, 3)
+        sc = 1.0 if fix_scale else rng.uniform(0.8, 1.25)
+        Xc1 = np.zeros((0, 3))
+        while len(Xc1) < n:   # points in front of both cameras
+            m = 2 * (n - len(Xc1)) + 8
+            u, v, z = rng.uniform(0, cam["width"], m), rng.uniform(0, cam["height"], m), rng.uniform(4, 40, m)
+            X = np.stack([(u - cx) * z / fx, (v - cy) * z / fy, z], 1)
+            X2 = (X - t12) @ R12 / sc
+            Xc1 = np.concatenate([Xc1, X[X2[:, 2] > 1.0]])
+        Xc1 = Xc1[:n]
+        Xc2 = (Xc1 - t12) @ R12 / sc   # S12^-1: R^T (x - t) / s
+        poses = []
+        for _ in range(2):
+            Rcw = _rot_y(rng.uniform(-180, 180)) @ _small_rot(rng, 3.0)
+            tcw = -Rcw @ np.array([rng.uniform(-50, 50), rng.uniform(-2, 2), rng.uniform(-50, 50)])
+            poses.append((Rcw, tcw))
+        Xw1 = (Xc1 - poses[0][1]) @ poses[0][0]
+        Xw2 = (Xc2 - poses[1][1]) @ poses[1][0]
+        oct1, oct2 = rng.integers(0, 8, n), rng.integers(0, 8, n)
+        z1 = np.stack([Xc1[:, 0] / Xc1[:, 2] * fx + cx, Xc1[:, 1] / Xc1[:, 2] * fy + cy], 1)
+        z2 = np.stack([Xc2[:, 0] / Xc2[:, 2] * fx + cx, Xc2[:, 1] / Xc2[:, 2] * fy + cy], 1)
+        if noise:
+            z1 = z1 + rng.normal(0, 1, (n, 2)) * (1.2 ** oct1)[:, None]
+            z2 = z2 + rng.normal(0, 1, (n, 2)) * (1.2 ** oct2)[:, None]
+        out = np.zeros(n, bool)
+        out[rng.permutation(n)[:n_out[p]]] = True
+        z2 = z2 + out[:, None] * rng.choice([-1, 1], (n, 2)) * rng.uniform(15, 40, (n, 2))
+        # keyframe 1: the n correspondences and 3 x extras dropped slots, shuffled; keyframe 2: permuted
+        e = extras
+        n1, n2 = n + 3 * e, n + 2 * e
+        order1, perm2 = rng.permutation(n1), rng.permutation(n2)
+        xy1 = np.concatenate([z1, rng.uniform(0, 300, (3 * e, 2))])
+        xw1 = np.concatenate([Xw1, rng.uniform(-5, 5, (3 * e, 3))])
+        o1 = np.concatenate([oct1, rng.integers(0, 8, 3 * e)])
+        val1 = np.concatenate([np.ones(n, bool), np.zeros(e, bool), np.ones(2 * e, bool)])
+        # slot of keyframe 2 before its permutation: i for the correspondences, a valid extra for the "no map
+        # point in keyframe 1" kind, -1, and a bad map point of keyframe 2
+        m12 = np.concatenate([np.arange(n), n + np.arange(e), -np.ones(e, int), n + e + np.arange(e)]).astype(int)
+        xy2 = np.concatenate([z2, rng.uniform(0, 300, (2 * e, 2))])
+        xw2 = np.concatenate([Xw2, rng.uniform(-5, 5, (2 * e, 3))])
+        o2 = np.concatenate([oct2, rng.integers(0, 8, 2 * e)])
+        val2 = np.concatenate([np.ones(n + e, bool), np.zeros(e, bool)])
+        inv2 = np.empty(n2, int)
+        inv2[perm2] = np.arange(n2)   # row r of keyframe 2 before the permutation sits at inv2[r]
+        m12 = np.where(m12 >= 0, inv2[np.maximum(m12, 0)], -1)
+        col["kp1_xy"].append(xy1[order1]); col["kp1_octave"].append(o1[order1]); col["mp1_valid"].append(val1[order1])
+        col["mp1_xw"].append(xw1[order1]); col["match12"].append(m12[order1])
+        col["outlier"].append(np.concatenate([out, np.zeros(3 * e, bool)])[order1])
+        col["kp2_xy"].append(xy2[perm2]); col["kp2_octave"].append(o2[perm2]); col["mp2_valid"].append(val2[perm2])
+        col["mp2_xw"].append(xw2[perm2])
+        kp1_begin.append(kp1_begin[-1] + n1)
+        kp2_begin.append(kp2_begin[-1] + n2)
+        pose1.append(np.concatenate([poses[0][0].reshape(-1), poses[0][1]]))
+        pose2.append(np.concatenate([poses[1][0].reshape(-1), poses[1][1]]))
+        gt.append(np.concatenate([R12.reshape(-1), t12, [sc]]))
+        R0 = _small_rot(rng, rot_deg) @ R12
+        t0 = t12 + rng.normal(0, trans, 3)
+        s0 = sc if fix_scale else sc * (1 + rng.normal(0, dscale))
+        s12.append(np.concatenate([R0.reshape(-1), t0, [s0]]))
+    cat = lambda k, w, dt: (np.concatenate(col[k]) if col[k] else np.zeros(0)).reshape((-1, w) if w > 1 else (-1,)).astype(dt)   # noqa: E731
+    levels = np.arange(8)
+    return dict(kp1_begin=np.array(kp1_begin, np.int32), kp2_begin=np.array(kp2_begin, np.int32),
+                kp1_xy=cat("kp1_xy", 2, np.float32), kp1_octave=cat("kp1_octave", 1, np.int32),
+                kp2_xy=cat("kp2_xy", 2, np.float32), kp2_octave=cat("kp2_octave", 1, np.int32),
+                pose1=f32(pose1).reshape(F, 12), camera1=np.tile(camv, (F, 1)),
+                pose2=f32(pose2).reshape(F, 12), camera2=np.tile(camv, (F, 1)),
+                mp1_valid=cat("mp1_valid", 1, np.uint8), mp1_xw=cat("mp1_xw", 3, np.float32),
+                mp2_valid=cat("mp2_valid", 1, np.uint8), mp2_xw=cat("mp2_xw", 3, np.float32),
+                s12=f32(s12).reshape(F, 13), match12=cat("match12", 1, np.int32),
+                inv_level_sigma2=(1.0 / (1.2 ** levels) ** 2).astype(np.float32), max_chi2=float(max_chi2),
+                fix_scale=int(bool(fix_scale)), gt_s12=np.array(gt).reshape(F, 13), outlier=cat("outlier", 1, bool),
+                n_corr=np.array(counts, np.int32))
