@@ -86,6 +86,7 @@ struct orbx_extractor {
     uint32_t fault_host = 0;   // test hook (ORBX_DEBUG_NC): shrink the quadtree node capacity to induce FAULT_QT_NODES
     int pyr_mfma = 0;   // ORBX_PYR_MFMA=1: pyramid_pair_mfma_kernel where the level pair's tables fit (measured slower: DESIGN §4)
     std::vector<char> pyr_mfma_ok;   // per level l: the pair (l, l+1) fits pyramid_pair_mfma_kernel
+    std::vector<int> pyr_pair_np;    // per level l: pyramid_pair_kernel's NP for the pair (l, l+1), 0: does not fit (pyr_pair_fits)
     DevBuf d_pyrmt, d_pyrkb;         // its A / C fragments per 16-column block, and the blocks' first tap column
     int pyr_pair = 2;   // pyramid_pair_kernel for levels (1,2), (3,4), (5,6) (level 0 16-byte aligned); 1: (2,3), (4,5), (6,7) (ORBX_PYR_PAIR)
     // OpenCV-build switches (orbx_set_opencv_compat; ORBX_TRIG / ORBX_RESIZE_TAIL)
@@ -216,44 +217,14 @@ static int setup_geometry(orbx_extractor* h, int rows, int cols) {
             L.stride = (int)align_up(L.w, 16);
             L.off = pyr_off;
             pyr_off += (long long)align_up((size_t)L.stride * L.h, 256);
-            // cv::resize tables (same arithmetic as the oracle / OpenCV)
-            const int sw = prev_w, sh = prev_h, dw = L.w, dh = L.h;
-            const double scale_x = 1. / ((double)dw / sw), scale_y = 1. / ((double)dh / sh);
+            // cv::resize tables (same arithmetic as the oracle / OpenCV: pyr_resize_tables)
             L.xtab_off = (int)xtab.size();
             L.ytab_off = (int)ytab.size();
-            L.ssx = (double)sw / L.w;
-            L.ssy = (double)sh / L.h;
+            L.ssx = (double)prev_w / L.w;
+            L.ssy = (double)prev_h / L.h;
             L.tail_x = resize_tail_x(L.w, h->resize_simd);
-            int xmax = dw;
-            std::vector<int> sxs(dw), a0s(dw), a1s(dw);
-            for (int dx = 0; dx < dw; dx++) {
-                float fx = (float)((dx + 0.5) * scale_x - 0.5);
-                int sx = (int)std::floor(fx);
-                fx -= sx;
-                if (sx < 0) { fx = 0; sx = 0; }
-                if (sx + 1 >= sw) {
-                    xmax = std::min(xmax, dx);
-                    if (sx >= sw - 1) { fx = 0; sx = sw - 1; }
-                }
-                sxs[dx] = sx;
-                a0s[dx] = std::min(std::max(cv_round_f((1.f - fx) * 2048), -32768), 32767);
-                a1s[dx] = std::min(std::max(cv_round_f(fx * 2048), -32768), 32767);
-            }
-            for (int dx = 0; dx < dw; dx++) {
-                int sx0 = sxs[dx], sx1 = std::min(sxs[dx] + 1, sw - 1), a0 = a0s[dx], a1 = a1s[dx];
-                if (dx >= xmax) { sx1 = sx0; a0 = 2048; a1 = 0; }
-                xtab.push_back(make_int2(sx0 | (sx1 << 16), (a0 & 0xffff) | (a1 << 16)));
-            }
-            L.mt_off = h->pyr_mfma ? pyr_mfma_tables(xtab.data() + L.xtab_off, dw, mt, mkb) : -1;
-            for (int dy = 0; dy < dh; dy++) {
-                float fy = (float)((dy + 0.5) * scale_y - 0.5);
-                int sy = (int)std::floor(fy);
-                fy -= sy;
-                const int b0 = std::min(std::max(cv_round_f((1.f - fy) * 2048), -32768), 32767);
-                const int b1 = std::min(std::max(cv_round_f(fy * 2048), -32768), 32767);
-                auto clip = [&](int y) { return y < 0 ? 0 : (y >= sh ? sh - 1 : y); };
-                ytab.push_back(make_int2(clip(sy) | (clip(sy + 1) << 16), (b0 & 0xffff) | (b1 << 16)));
-            }
+            pyr_resize_tables(prev_w, prev_h, L.w, L.h, xtab, ytab);
+            L.mt_off = h->pyr_mfma ? pyr_mfma_tables(xtab.data() + L.xtab_off, L.w, mt, mkb) : -1;
         }
         if (l > 0) {   // the pyramid kernel's LDS source tile must hold a 64x16 output tile's footprint
             const double sc = (double)prev_w / L.w, scy = (double)prev_h / L.h;
@@ -419,6 +390,8 @@ static int setup_geometry(orbx_extractor* h, int rows, int cols) {
         ORB_HIP_TRY(hipMemcpy(h->d_pyrkb.ptr, mkb.data(), mkb.size() * sizeof(int), hipMemcpyHostToDevice));
     h->pyr_mfma_ok.assign(Lc, 0);
     for (int l = 1; l + 1 < Lc; l++) h->pyr_mfma_ok[l] = h->pyr_mfma && pyr_mfma_pair_fits(g, l, mkb, ytab);
+    h->pyr_pair_np.assign(Lc, 0);
+    for (int l = 1; l + 1 < Lc; l++) h->pyr_pair_np[l] = pyr_pair_fits(g, l, xtab, ytab);
     h->geom = g;
     h->cells = cells;
     {   // FAST column strips: up to fast_cpw vertically consecutive cells of one column per wavefront
@@ -640,9 +613,9 @@ static void launch_chunk(orbx_extractor* h, int f0, const uint8_t* d_imgs, int F
                          h->d_ytab.as<int2>(), h->d_pyrmt.as<PyrMfmaLane>(), h->d_pyrkb.as<int>());
             return 1;
         }
-        if (pair && pyr_pair_fits(g, l)) {
-            launch_timed(h, 0, pyramid_pair_kernel, tiles(l + 1), dim3(256), 0u, st, g, l, d_imgs, fstride, step, pyr,
-                         h->d_xtab.as<int2>(), h->d_ytab.as<int2>());
+        if (pair && h->pyr_pair_np[l]) {
+            launch_timed(h, 0, h->pyr_pair_np[l] <= 7 ? pyramid_pair_kernel<7> : pyramid_pair_kernel<PP_MAXP>, tiles(l + 1),
+                         dim3(256), 0u, st, g, l, d_imgs, fstride, step, pyr, h->d_xtab.as<int2>(), h->d_ytab.as<int2>());
             return 1;
         }
         launch_timed(h, 0, pyramid_level_kernel, tiles(l), dim3(256), 0u, st, g, l, d_imgs, fstride, step, pyr,

@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "orbx_geom.h"
+#include "orbx_pyr_rect.h"
 
 namespace orbamd {
 
@@ -48,8 +49,16 @@ __device__ __forceinline__ us2 pyr_tap(uint32_t hi, uint32_t lo, uint32_t sel) {
     return *reinterpret_cast<const us2*>(&r);
 }
 
-constexpr int PYR_TW = 64, PYR_TH = 64;
-constexpr int PYR_SW = 144, PYR_SH = 128;   // LDS source tile capacity (scale factor <= ~1.9)
+// (tile and LDS capacities: orbx_pyr_rect.h)
+// pyr_recip20 as a table: a workgroup's divisions by its piece / quad counts are one scalar load each
+struct PyrRecipTab { unsigned m[PYR_RECIP_N]; };
+constexpr PyrRecipTab pyr_recip_tab() {
+    PyrRecipTab t{};
+    for (int n = 1; n < PYR_RECIP_N; n++) t.m[n] = pyr_recip20(n);
+    return t;
+}
+__constant__ PyrRecipTab c_pyr_recip = pyr_recip_tab();
+static_assert(PYR_SW / 16 < PYR_RECIP_N, "the staging piece counts are in the table");
 
 // A tile row's vertical taps, built once per workgroup (round 4): the byte offsets of its two source rows
 // in the staged rectangle (first row sy_lo, row stride PYR_SW) and the two coefficients in mulhi24 form
@@ -175,7 +184,7 @@ __device__ __forceinline__ void pyr_tile_compute(const Geom& g, const LevelDev& 
 // 16-byte staging (every pyramid level; level 0 when the caller's base and step are multiples of
 // 16): the source rectangle is fetched as 16-byte pieces with (row, piece) flattened over the 256
 // threads, i.e. ~3 loads per thread instead of one dword load per source row.
-constexpr int PYR_PF = 5;   // 16-byte pieces per thread: PYR_SH rows x PYR_SW / 16 pieces <= 5 x 256
+// (PYR_PF 16-byte pieces per thread: rows x pieces <= 5 x 256)
 
 struct PyrTile {
     int f, tx0, ty0, tw, th, sy_lo, xa, nc, items, mul;   // mul = ceil(2^20 / nc): row = item * mul >> 20
@@ -183,10 +192,10 @@ struct PyrTile {
     int sstep;
 };
 
-__device__ __forceinline__ PyrTile pyr_tile_geom(const Geom& g, int l, int t, int ntx, int nty, const uint8_t* in,
-                                                 long long in_fstride, int in_step, uint8_t* pyr) {
+// (sx, sy: the source spans the tile's taps cover, pyr_tap_span)
+__device__ __forceinline__ PyrTile pyr_tile_geom(const Geom& g, int l, int t, int ntx, int nty, PyrSpan sx, PyrSpan sy,
+                                                 const uint8_t* in, long long in_fstride, int in_step, uint8_t* pyr) {
     const LevelDev& L = g.lv[l];
-    const LevelDev& Ls = g.lv[l - 1];
     PyrTile T;
     const int per = ntx * nty;
     T.f = t / per;
@@ -195,14 +204,11 @@ __device__ __forceinline__ PyrTile pyr_tile_geom(const Geom& g, int l, int t, in
     T.tx0 = (r - (r / ntx) * ntx) * PYR_TW;
     T.tw = min(PYR_TW, L.w - T.tx0);
     T.th = min(PYR_TH, L.h - T.ty0);
-    const int sx_lo = max(0, (int)floor((T.tx0 + 0.5) * L.ssx - 0.5) - 2);
-    const int sx_hi = min(Ls.w - 1, (int)floor((T.tx0 + T.tw - 0.5) * L.ssx - 0.5) + 2);
-    T.sy_lo = max(0, (int)floor((T.ty0 + 0.5) * L.ssy - 0.5) - 2);
-    const int sy_hi = min(Ls.h - 1, (int)floor((T.ty0 + T.th - 0.5) * L.ssy - 0.5) + 2);
-    T.xa = sx_lo & ~15;
-    T.nc = ((sx_hi - T.xa) >> 4) + 1;
-    T.items = (sy_hi - T.sy_lo + 1) * T.nc;
-    T.mul = ((1 << 20) + T.nc - 1) / T.nc;
+    T.sy_lo = sy.lo;
+    T.xa = sx.lo & ~15;
+    T.nc = ((sx.hi - T.xa) >> 4) + 1;
+    T.items = (sy.hi - sy.lo + 1) * T.nc;
+    T.mul = (int)c_pyr_recip.m[T.nc];
     T.src = level_base(g, l - 1, T.f, in, in_fstride, in_step, pyr, &T.sstep);
     // workgroup-uniform by construction: keep the tile in SGPRs, not in VGPRs across the compute
     auto u = [](int x) { return __builtin_amdgcn_readfirstlane(x); };
@@ -265,24 +271,23 @@ __global__ __launch_bounds__(256) void pyramid_level_kernel(Geom g, int l, const
     const uint8_t* src = level_base(g, l - 1, f, in, in_fstride, in_step, pyr, &sstep);
     const int2* xt = xtab + L.xtab_off;
     const int2* yt = ytab + L.ytab_off;
-    // coefficient tables -> LDS (independent of the image loads below)
-    // conservative source rectangle from the scale (a superset of the tables' taps; no table
-    // round trip before the image loads)
-    const int sw = Ls.w, sh = Ls.h;
-    const double scx = L.ssx, scy = L.ssy;
-    const int sx_lo = max(0, (int)floor((tx0 + 0.5) * scx - 0.5) - 2);
-    const int sx_hi = min(sw - 1, (int)floor((tx0 + tw - 0.5) * scx - 0.5) + 2);
-    const int sy_lo = max(0, (int)floor((ty0 + 0.5) * scy - 0.5) - 2);
+    // the source rectangle the tile's taps cover, from the first and last entries of its table rows
+    // (workgroup-uniform reads)
+    const int sw = Ls.w;
+    const PyrSpan sx = pyr_tap_span(xt, tx0, tx0 + tw - 1), sy = pyr_tap_span(yt, ty0, ty0 + th - 1);
+    const int sx_lo = __builtin_amdgcn_readfirstlane(sx.lo), sx_hi = __builtin_amdgcn_readfirstlane(sx.hi);
+    const int sy_lo = __builtin_amdgcn_readfirstlane(sy.lo), sy_hi = __builtin_amdgcn_readfirstlane(sy.hi);
+    // coefficient tables -> LDS
     if ((int)threadIdx.x < tw) xs_t[threadIdx.x] = xt[tx0 + threadIdx.x];
     if ((int)threadIdx.x >= 64 && (int)threadIdx.x - 64 < th)
         ys_t[threadIdx.x - 64] = pyr_row_taps(yt[ty0 + threadIdx.x - 64], sy_lo);
-    const int sy_hi = min(sh - 1, (int)floor((ty0 + th - 0.5) * scy - 0.5) + 2);
     const int xa = sx_lo & ~3;
     const int nd = (sx_hi - xa + 4) >> 2;   // dwords per source row (<= PYR_SW / 4 < 64)
     const int nr = sy_hi - sy_lo + 1;
     const bool aligned = ((reinterpret_cast<uintptr_t>(src) | (uintptr_t)sstep) & 3) == 0;
     if (((reinterpret_cast<uintptr_t>(src) | (uintptr_t)sstep) & 15) == 0 && sx_hi - (sx_lo & ~15) < PYR_SW) {
-        const PyrTile T = pyr_tile_geom(g, l, lb, gx, gridDim.y, in, in_fstride, in_step, pyr);
+        const PyrTile T = pyr_tile_geom(g, l, lb, gx, gridDim.y, PyrSpan{sx_lo, sx_hi}, PyrSpan{sy_lo, sy_hi}, in,
+                                        in_fstride, in_step, pyr);
         uint4 v0, v1, v2, v3, v4;
         pyr_fetch(T, threadIdx.x, v0, v1, v2, v3, v4);
         pyr_stage(T, threadIdx.x, S, v0, 0);
@@ -332,13 +337,11 @@ __global__ __launch_bounds__(256) void pyramid_level_kernel(Geom g, int l, const
 
 // Two cascaded levels in one launch: level l (from level l-1, both in the pyramid slab) and level
 // l+1, one workgroup per 64x64 tile of level l+1.  The workgroup computes the level-l rectangle
-// its tile's taps need (the conservative rectangle of pyramid_level_kernel, columns from a dword
-// boundary) from a staged level-(l-1) rectangle, keeps it in LDS for the level-(l+1) tile and
-// writes it to the slab.  Neighbouring workgroups' rectangles overlap by the tap margins; they
-// write the same bytes there.  Removes the launch boundary between the two levels and the
-// level-l re-read.
-constexpr int PP_MAXP = 8;   // level-l row passes per thread
-constexpr int PP_MAXC = 96, PP_MAXR = 96;   // level-l rectangle columns / rows the tables hold
+// its tile's taps cover (pyr_pair_rect: read from the tap tables, columns from a dword boundary)
+// from a staged level-(l-1) rectangle, keeps it in LDS for the level-(l+1) tile and writes it to
+// the slab.  Neighbouring workgroups' rectangles overlap where both tiles tap a pixel; they write
+// the same bytes there.  Removes the launch boundary between the two levels and the level-l
+// re-read.  NP: the level-l row passes the host found over every tile of the pair (pyr_pair_fits).
 
 __device__ __forceinline__ uint32_t pyr_px_generic(const uint8_t* S, int2 xv, int4 yv, int xa, bool tail) {
     const int r0 = yv.x, r1 = yv.y;
@@ -352,6 +355,7 @@ __device__ __forceinline__ uint32_t pyr_px_generic(const uint8_t* S, int2 xv, in
     return (uint32_t)(v > 255 ? 255 : v);
 }
 
+template <int NP>
 __global__ __launch_bounds__(256) void pyramid_pair_kernel(Geom g, int l, const uint8_t* __restrict__ in,
                                                            long long in_fstride, int in_step, uint8_t* pyr,
                                                            const int2* __restrict__ xtab,
@@ -359,7 +363,6 @@ __global__ __launch_bounds__(256) void pyramid_pair_kernel(Geom g, int l, const 
     __shared__ __attribute__((aligned(16))) uint8_t S[PYR_SH * PYR_SW + 16];
     __shared__ int2 xs1[PP_MAXC], xs2[PYR_TW];
     __shared__ int4 ys1[PP_MAXR], ys2[PYR_TH];
-    const LevelDev& L0 = g.lv[l - 1];
     const LevelDev& L1 = g.lv[l];
     const LevelDev& L2 = g.lv[l + 1];
     const int tid = threadIdx.x;
@@ -369,23 +372,18 @@ __global__ __launch_bounds__(256) void pyramid_pair_kernel(Geom g, int l, const 
     const int tx0 = (lb % gx) * PYR_TW, ty0 = ((lb % gxy) / gx) * PYR_TH;
     const int tw = min(PYR_TW, L2.w - tx0), th = min(PYR_TH, L2.h - ty0);
     auto u = [](int x) { return __builtin_amdgcn_readfirstlane(x); };
-    // level-l rectangle [c0, c1] x [ay0, ay1] (c0 dword aligned)
-    const int ax0 = max(0, (int)floor((tx0 + 0.5) * L2.ssx - 0.5) - 2);
-    const int c1 = u(min(L1.w - 1, (int)floor((tx0 + tw - 0.5) * L2.ssx - 0.5) + 2));
-    const int ay0 = u(max(0, (int)floor((ty0 + 0.5) * L2.ssy - 0.5) - 2));
-    const int ay1 = u(min(L1.h - 1, (int)floor((ty0 + th - 0.5) * L2.ssy - 0.5) + 2));
-    const int c0 = u(ax0 & ~3);
+    // level-l rectangle [c0, c1] x [ay0, ay1] (c0 dword aligned) and the level-(l-1) rectangle for it,
+    // staged as 16-byte pieces: workgroup-uniform reads of the tables' first / last entries
+    const PyrPairRect R = pyr_pair_rect(xtab + L1.xtab_off, ytab + L1.ytab_off, xtab + L2.xtab_off,
+                                        ytab + L2.ytab_off, tx0, ty0, tw, th);
+    const int c0 = u(R.c0), c1 = u(R.c1), ay0 = u(R.ay0), ay1 = u(R.ay1);
     const int ncol = c1 - c0 + 1, nrow = ay1 - ay0 + 1;
-    // level-(l-1) rectangle for it, staged as 16-byte pieces
     PyrTile T;
-    const int bx0 = max(0, (int)floor((c0 + 0.5) * L1.ssx - 0.5) - 2);
-    const int bx1 = min(L0.w - 1, (int)floor((c1 + 0.5) * L1.ssx - 0.5) + 2);
-    T.sy_lo = u(max(0, (int)floor((ay0 + 0.5) * L1.ssy - 0.5) - 2));
-    const int by1 = min(L0.h - 1, (int)floor((ay1 + 0.5) * L1.ssy - 0.5) + 2);
-    T.xa = u(bx0 & ~15);
-    T.nc = u(((bx1 - T.xa) >> 4) + 1);
-    T.items = u((by1 - T.sy_lo + 1) * T.nc);
-    T.mul = u(((1 << 20) + T.nc - 1) / T.nc);
+    T.sy_lo = u(R.by0);
+    T.xa = u(R.xa);
+    T.nc = u(((R.bx1 - R.xa) >> 4) + 1);
+    T.items = u((R.by1 - R.by0 + 1) * T.nc);
+    T.mul = u((int)c_pyr_recip.m[T.nc]);
     T.src = level_base(g, l - 1, f, in, in_fstride, in_step, pyr, &T.sstep);   // 16-byte aligned (host)
     {
         uint4 v0, v1, v2, v3, v4;
@@ -401,11 +399,14 @@ __global__ __launch_bounds__(256) void pyramid_pair_kernel(Geom g, int l, const 
         pyr_stage(T, tid, S, v4, 4);
     }
     __syncthreads();
-    // level l: thread = (quad q of 4 columns, first row r0), rows r0 + p * rpp
-    const int ncq = (ncol + 3) >> 2, rpp = 256 / ncq;
-    const int q = tid % ncq, r0 = tid / ncq;
+    // level l: thread = (quad q of 4 columns, first row r0), rows r0 + p * rpp; tid / ncq by the
+    // table's reciprocal (exact for tid <= 2048), rpp = 256 / ncq likewise
+    const int ncq = (ncol + 3) >> 2;
+    const unsigned m20 = (unsigned)u((int)c_pyr_recip.m[ncq]);
+    const int rpp = (int)(m20 >> 12);
+    const int r0 = (int)(__umul24((unsigned)tid, m20) >> 20), q = tid - __mul24(r0, ncq);
     const bool act = r0 < rpp;
-    uint32_t out[PP_MAXP];
+    uint32_t out[NP];
     if (act) {
         uint32_t sel0[2], sel1[2], wdv[2];
         us2 a0[2], a1[2];
@@ -432,10 +433,13 @@ __global__ __launch_bounds__(256) void pyramid_pair_kernel(Geom g, int l, const 
         auto rows = [&](auto tail_c) {
             constexpr bool TAIL = decltype(tail_c)::value;
 #pragma unroll
-            for (int pp = 0; pp < PP_MAXP; pp++) {
+            for (int pp = 0; pp < NP; pp++) {
                 const int r = r0 + pp * rpp;
                 out[pp] = 0;
-                if (r >= nrow) break;
+                // workgroup-uniform: the pass is empty / every row of it exists (the per-thread row
+                // test runs on the rectangle's last pass only)
+                if (pp * rpp >= nrow) break;
+                if ((pp + 1) * rpp > nrow && r >= nrow) break;
                 const int4 yv = ys1[r];
                 if (fits) {
                     const uint32_t b0 = (uint32_t)yv.z, b1 = (uint32_t)yv.w;   // b << 12 (pyr_row_taps)
@@ -473,9 +477,10 @@ __global__ __launch_bounds__(256) void pyramid_pair_kernel(Geom g, int l, const 
         // neighbouring workgroup writes the true ones there)
         const bool full = c0 + 4 * q + 3 <= c1;
 #pragma unroll
-        for (int pp = 0; pp < PP_MAXP; pp++) {
+        for (int pp = 0; pp < NP; pp++) {
             const int r = r0 + pp * rpp;
-            if (r >= nrow) break;
+            if (pp * rpp >= nrow) break;
+            if ((pp + 1) * rpp > nrow && r >= nrow) break;
             *reinterpret_cast<uint32_t*>(&S[r * PYR_SW + 4 * q]) = out[pp];
             uint8_t* dst = lrow + __mul24(ay0 + r, L1.stride);
             if (full) {
@@ -490,16 +495,15 @@ __global__ __launch_bounds__(256) void pyramid_pair_kernel(Geom g, int l, const 
     pyr_tile_compute(g, L2, f, pyr, S, xs2, ys2, tx0, ty0, tw, th, c0);
 }
 
-// Host check of pyramid_pair_kernel's capacities at the level pair's scale factors (with margins
-// for the floor / alignment slack of the conservative rectangles).
-static bool pyr_pair_fits(const Geom& g, int l) {
-    const double s1x = g.lv[l].ssx, s1y = g.lv[l].ssy, s2x = g.lv[l + 1].ssx, s2y = g.lv[l + 1].ssy;
-    const int ncol = (int)std::ceil(PYR_TW * s2x) + 10, nrow = (int)std::ceil(PYR_TH * s2y) + 7;
-    const int ncq = (ncol + 3) / 4, rpp = 256 / ncq;
-    const int bw = (int)std::ceil(ncol * s1x) + 7 + 15, bh = (int)std::ceil(nrow * s1y) + 7;
-    return ncol + 8 <= PYR_SW && nrow <= PYR_SH && ncol <= PP_MAXC && nrow <= PP_MAXR && (nrow + rpp - 1) / rpp <= PP_MAXP &&
-           bw <= PYR_SW && bh <= PYR_SH &&
-           bh * ((bw + 15) / 16) <= PYR_PF * 256;
+// Host check of pyramid_pair_kernel for the pair (l, l+1): the kernel's geometry replayed for every
+// tile from the host's copy of the tap tables (pyr_pair_plan).  Returns the NP to launch (the pass
+// count rounded up to an instantiated one), 0 when a tile exceeds a capacity.
+static int pyr_pair_fits(const Geom& g, int l, const std::vector<int2>& xtab, const std::vector<int2>& ytab) {
+    const LevelDev &L0 = g.lv[l - 1], &L1 = g.lv[l], &L2 = g.lv[l + 1];
+    const PyrPairPlan P = pyr_pair_plan(L0.w, L0.h, L1.w, L1.h, L2.w, L2.h, xtab.data() + L1.xtab_off,
+                                        ytab.data() + L1.ytab_off, xtab.data() + L2.xtab_off, ytab.data() + L2.ytab_off);
+    if (!P.ok) return 0;
+    return P.passes <= 7 ? 7 : PP_MAXP;
 }
 
 // ---- the level pair with the horizontal pass on the matrix cores (round 5) ----
