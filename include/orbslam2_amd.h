@@ -850,6 +850,101 @@ int orbba_optimize_sim3(const orbba_sim3_batch* in, orbba_sim3_result* out, int 
  * pair. */
 int orbba_optimize_sim3_device(const orbba_sim3_batch* in, orbba_sim3_result* out, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Sim3Solver(keyframe1, keyframe2, matches, fixScale), SetRansacParameters(probability, minInliers,
+ * maxIterations) and bool Sim3Solver::iterate(int maxk, Sim3& sim3, std::vector<bool>& isInlier)
+ * (include/Sim3Solver.h, src/Sim3Solver.cc:206-365; LoopClosing::FindLoopInCandidateKFs, LoopClosing.cc:105-135:
+ * 0.99, 20, 300, iterate(5)), batched over (keyframe1, keyframe2) pairs in orbm_sim3_batch's slot layout, so
+ * orbm_search_by_bow_kf_batch_device's match12 feeds straight in and the outputs feed orbm_search_by_sim3_device
+ * and orbba_optimize_sim3_device.
+ * Correspondences (:225-255): slot i1 of keyframe 1, ascending, is kept iff mp1_valid[i1] && match12[i1] >= 0 &&
+ * mp2_valid[match12[i1]]; i1 stands for GetIndexInKeyFrame(keyframe1) and match12[i1] for
+ * GetIndexInKeyFrame(keyframe2), the convention of orbba_optimize_sim3.  Per kept correspondence, in float:
+ * Xc1 = R1w * Xw1 + t1w, Xc2 = R2w * Xw2 + t2w, points{1,2} = FromCameraToImage(Xc{1,2}) (invZ = 1 / z,
+ * fx * (x * invZ) + cx; :186-204), and in double maxErrorSq{1,2} = 9.21 * (double)level_sigma2[octave].  The
+ * keypoint positions are not read (kp1_xy, kp2_xy and s12 keep orbba_sim3_batch's layout and may be NULL).
+ * Iteration cap (:266-287): with nmatches the kept count, epsilon = 1.f * min_inliers / nmatches (float),
+ * niterations = 1 when min_inliers == nmatches, else ceil(log(1 - probability) / log(1 - pow(epsilon, 3))) in
+ * double, cap = max(1, min(niterations, max_iterations)) (compared in double before narrowing to int).  The
+ * host computes cap for every nmatches in 0 .. ORBM_PROJ_MAX_KP with libm and the kernel indexes that table.
+ * Sampling (:307-322): DUtils::Random::RandomInt is libc rand(), so the draws are an input: hypothesis k of
+ * pair p uses draws[p, k, 0..2], raw rand() values in [0, rand_max]; draw c picks position
+ * int(((double)r / ((double)rand_max + 1.0)) * (nmatches - c)) of the available indices, which is then refilled
+ * from the back and popped (three draws without replacement).  A result therefore does not depend on how the
+ * iterations are split over calls.  The reference interleaves one global rand() stream over the candidates in
+ * round-robin order; a table per pair is statistically the same and not a replay of a particular CPU run.
+ * Hypothesis (ComputeSim3, :111-163), float unless said: centroids ((P(i,0) + P(i,1)) + P(i,2)) / 3.f;
+ * M = Pr2 * Pr1^T with ((a0 b0 + a1 b1) + a2 b2); R12 = U S Vh of svd(M^T) with S(2,2) = -1 when
+ * det(U) det(Vh) < 0, computed in fp64 from the float M as Horn's unit quaternion (the same proper rotation,
+ * DESIGN.md section 4) and rounded to float; P3 = R12 * Pr2; s12 = (float)(nom / den), nom = Pr1.dot(P3) with
+ * products and sum in double, den = the float products P3(i,j) * P3(i,j) added to a double, both row-major; 1
+ * exactly with fix_scale; t12 = O1 - (s12 * R12) * O2; S21 = S12.Inverse() (Sim3.h:43-47: R21 = R12^T,
+ * t21 = ((-(1 / s)) * R12^T) * t12, s21 = 1 / s).
+ * Scoring (:327-344): proj1 = Project(Xc2, S12, camera1), proj2 = Project(Xc1, S21, camera2) with Sim3::Map
+ * ((s * R) * x + t), invZ = 1.f / z and no depth test; errorSq = dx * dx + dy * dy in float, widened, and a
+ * correspondence is an inlier iff errorSq1 < maxErrorSq1 && errorSq2 < maxErrorSq2 (IEEE: a zero or negative
+ * depth gives inf or NaN, never an inlier).  n[k] = the inlier count of hypothesis k.
+ * Control (:289-365), per pair, on the state (iterations, max_inliers) that the call reads and writes:
+ * nmatches < min_inliers: terminate = 1, found = 0, the state unchanged.  Otherwise k runs over
+ * [iterations, min(iterations + maxk, cap)); k updates iff n[k] >= max_inliers (then max_inliers = n[k]) and
+ * succeeds iff it updates and n[k] > min_inliers.  At the first success: found = 1, iterations = k + 1, s12 =
+ * that hypothesis, inlier[i1] = 1 for the slots of its inliers, match12[i1] = the input's for those slots and
+ * -1 elsewhere (LoopClosing.cc:133-135), n_inliers = n[k].  Without one: found = 0, iterations =
+ * min(iterations + maxk, cap), terminate = (iterations >= cap), n_inliers = 0, and the pair's inlier is 0,
+ * its match12 -1 and its s12 row 0 everywhere (iterate() clears isInlier on entry; nothing is left unwritten). */
+typedef struct orb_sim3solver_batch {
+    int32_t        n_pairs, total_kp1, total_kp2;
+    const int32_t* kp1_begin;    /* n_pairs + 1 */
+    const int32_t* kp2_begin;    /* n_pairs + 1 */
+    const float*   kp1_xy;       /* not read; may be NULL */
+    const int32_t* kp1_octave;   /* total_kp1 */
+    const float*   kp2_xy;       /* not read; may be NULL */
+    const int32_t* kp2_octave;   /* total_kp2 */
+    const float*   pose1;        /* n_pairs x 12: Rcw (row-major 3x3) then tcw */
+    const float*   camera1;      /* n_pairs x 4: fx, fy, cx, cy */
+    const float*   pose2;
+    const float*   camera2;
+    const uint8_t* mp1_valid;    /* total_kp1: mappoints1[i] && !mappoints1[i]->isBad() */
+    const float*   mp1_xw;       /* total_kp1 x 3 */
+    const uint8_t* mp2_valid;    /* total_kp2: the map point of slot i2 exists and is not bad */
+    const float*   mp2_xw;       /* total_kp2 x 3 */
+    const float*   s12;          /* not read; may be NULL */
+    const int32_t* match12;      /* total_kp1: keyframe-2-relative index of matches[i1] or -1 */
+    int32_t        n_levels;
+    const float*   level_sigma2; /* host, n_levels (pyramid.sigmaSq) */
+    int32_t        fix_scale;    /* per batch */
+    const int32_t* draws;        /* n_pairs x max_iterations x 3: rand() values in [0, rand_max] */
+    int32_t        rand_max;     /* RAND_MAX of the generator that made draws (glibc: 2147483647) */
+    double         probability;  /* SetRansacParameters; in (0, 1) */
+    int32_t        min_inliers;  /* >= 3 */
+    int32_t        max_iterations; /* >= 1 */
+    int32_t        maxk;         /* iterate(maxk); >= 1 */
+} orb_sim3solver_batch;
+
+typedef struct orb_sim3solver_result {
+    float*   s12;          /* n_pairs x 13: R12 (row-major 3x3), t12, s of the successful hypothesis, else 0 */
+    uint8_t* inlier;       /* total_kp1: isInlier */
+    int32_t* match12;      /* total_kp1: inlier[i1] ? the input's match12[i1] : -1; must not alias the input */
+    int32_t* found;        /* n_pairs: iterate()'s return value; -1 from the device entry for a pair either of
+                            * whose keyframes has more than ORBM_PROJ_MAX_KP keypoints (its state unchanged,
+                            * terminate 1, the other outputs as without a success) */
+    int32_t* n_inliers;    /* n_pairs: the successful hypothesis's inlier count, else 0 */
+    int32_t* iterations;   /* n_pairs, in / out: iterations_ (0 for a fresh solver) */
+    int32_t* max_inliers;  /* n_pairs, in / out: maxInliers_ (0 for a fresh solver) */
+    int32_t* terminate;    /* n_pairs: terminate() */
+    int32_t* hyp_inliers;  /* n_pairs x max_iterations: n[k] of the hypotheses the reference would have
+                            * evaluated in this call, -1 elsewhere; may be NULL */
+} orb_sim3solver_result;
+
+/* Host entry: every pointer is host memory, synchronous; offsets, octaves, the range of match12, the state and
+ * draws in [0, rand_max] are validated before anything is copied; a keyframe with more than ORBM_PROJ_MAX_KP
+ * keypoints is refused. */
+int orb_sim3solver_iterate(const orb_sim3solver_batch* in, orb_sim3solver_result* out, int device);
+/* Device entry: every array in HBM except level_sigma2; enqueues only on `stream` (the first call with a new
+ * (probability, min_inliers, max_iterations) uploads its cap table synchronously, as the first call allocates
+ * the workspace).  A draw outside [0, rand_max] is clamped to a valid position.  One lane per hypothesis. */
+int orb_sim3solver_iterate_device(const orb_sim3solver_batch* in, orb_sim3solver_result* out, void* stream);
+
 const char* orb_last_error(void);
 int orb_device_count(void);
 

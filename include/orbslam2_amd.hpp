@@ -493,6 +493,33 @@ struct Optimizer {
     }
 };
 
+// Sim3Solver (include/Sim3Solver.h, src/Sim3Solver.cc:206-365): the 3-point RANSAC between SearchByBoW and
+// SearchBySim3 in LoopClosing::FindLoopInCandidateKFs, a solver per (keyframe1, keyframe2) pair in SearchBySim3's
+// slot layout (orb_sim3solver_batch: match12 is SearchByBoW's output, draws the rand() values of every hypothesis,
+// r.iterations / r.max_inliers the solvers' state, read and written).
+struct Sim3Solver {
+    // bool iterate(maxk, sim3, isInlier) of every pair's solver on HBM arrays.  Enqueue only: r.found = the return
+    // values, r.s12 the Sim3, r.inlier isInlier, r.match12 the input's matches thinned to the inliers.
+    static void IterateBatch(const orb_sim3solver_batch& b, orb_sim3solver_result& r, void* stream = nullptr) {
+        check(orb_sim3solver_iterate_device(&b, &r, stream), "orb_sim3solver_iterate_device");
+    }
+    // The same for one pair on host arrays.  iterations / max_inliers: the solver's state (0, 0 for a fresh one),
+    // in / out; s12: 13 floats R, t, s; returns iterate()'s value and sets terminate.
+    static bool Iterate(const orb_sim3solver_batch& b, int32_t& iterations, int32_t& max_inliers, float* s12,
+                        std::vector<uint8_t>& inlier, std::vector<int32_t>& match12, bool& terminate, int device = 0) {
+        if (b.n_pairs != 1) throw std::invalid_argument("Sim3Solver::Iterate: one pair per call (use the batch form)");
+        inlier.assign(std::max(b.total_kp1, 1), 0);
+        match12.assign(std::max(b.total_kp1, 1), -1);
+        int32_t found = 0, n_inliers = 0, term = 0;
+        orb_sim3solver_result r = {s12, inlier.data(), match12.data(), &found, &n_inliers, &iterations, &max_inliers, &term, nullptr};
+        check(orb_sim3solver_iterate(&b, &r, device), "orb_sim3solver_iterate");
+        inlier.resize(b.total_kp1);
+        match12.resize(b.total_kp1);
+        terminate = term != 0;
+        return found == 1;
+    }
+};
+
 // void MapPoint::ComputeDistinctiveDescriptors() (src/MapPoint.cc:257-320), batched over map points on HBM
 // arrays: point p holds the rows [begin[p], begin[p + 1]) of d_desc.  Enqueue only; best[p] = the winning
 // point-relative row (-1: empty), d_out_desc[p] = that row (an empty point's row is not written, so

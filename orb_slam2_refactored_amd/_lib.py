@@ -161,6 +161,26 @@ class OptSim3Result(C.Structure):
                 ("iterations", C.c_void_p)]
 
 
+class Sim3SolverBatch(C.Structure):
+    """orb_sim3solver_batch (include/orbslam2_amd.h)."""
+    _fields_ = [("n_pairs", C.c_int32), ("total_kp1", C.c_int32), ("total_kp2", C.c_int32),
+                ("kp1_begin", C.c_void_p), ("kp2_begin", C.c_void_p),
+                ("kp1_xy", C.c_void_p), ("kp1_octave", C.c_void_p), ("kp2_xy", C.c_void_p), ("kp2_octave", C.c_void_p),
+                ("pose1", C.c_void_p), ("camera1", C.c_void_p), ("pose2", C.c_void_p), ("camera2", C.c_void_p),
+                ("mp1_valid", C.c_void_p), ("mp1_xw", C.c_void_p), ("mp2_valid", C.c_void_p), ("mp2_xw", C.c_void_p),
+                ("s12", C.c_void_p), ("match12", C.c_void_p), ("n_levels", C.c_int32),
+                ("level_sigma2", C.c_void_p), ("fix_scale", C.c_int32), ("draws", C.c_void_p), ("rand_max", C.c_int32),
+                ("probability", C.c_double), ("min_inliers", C.c_int32), ("max_iterations", C.c_int32),
+                ("maxk", C.c_int32)]
+
+
+class Sim3SolverResult(C.Structure):
+    """orb_sim3solver_result (include/orbslam2_amd.h)."""
+    _fields_ = [("s12", C.c_void_p), ("inlier", C.c_void_p), ("match12", C.c_void_p), ("found", C.c_void_p),
+                ("n_inliers", C.c_void_p), ("iterations", C.c_void_p), ("max_inliers", C.c_void_p),
+                ("terminate", C.c_void_p), ("hyp_inliers", C.c_void_p)]
+
+
 # cv::KeyPoint layout (28 bytes)
 KP_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("size", "<f4"), ("angle", "<f4"),
                      ("response", "<f4"), ("octave", "<i4"), ("class_id", "<i4")])
@@ -230,7 +250,9 @@ SIGNATURES = {
     "orbba_pose_optimization_device": (C.c_int, [C.POINTER(PoseBatch), C.POINTER(PoseResult), VP]),
     "orbba_optimize_sim3": (C.c_int, [C.POINTER(OptSim3Batch), C.POINTER(OptSim3Result), C.c_int]),
     "orbba_optimize_sim3_device": (C.c_int, [C.POINTER(OptSim3Batch), C.POINTER(OptSim3Result), VP]),
-    "orbx_pack_descriptors": (C.c_int, [VP, C.c_int, VP, VP, C.c_int, VP, C.c_int, VP]),
+    "orb_sim3solver_iterate": (C.c_int, [C.POINTER(Sim3SolverBatch), C.POINTER(Sim3SolverResult), C.c_int]),
+    "orb_sim3solver_iterate_device": (C.c_int, [C.POINTER(Sim3SolverBatch), C.POINTER(Sim3SolverResult), VP]),
+    "orbx_pack_descriptors": (C.c_int,[VP, C.c_int, VP, VP, C.c_int, VP, C.c_int, VP]),
     "orbx_profile_enable": (C.c_int, [VP, C.c_int]),
     "orbx_profile_read": (C.c_int, [VP, VP, VP]),
     "orbx_debug_level_candidates": (C.c_int, [VP, C.c_int, C.c_int, VP, C.c_int, C.POINTER(C.c_int)]),

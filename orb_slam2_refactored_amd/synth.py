@@ -1075,3 +1075,44 @@ def make_optsim3_batch(seed: int = 0, n_corr=(150,), n_outliers=0, noise: bool =
                 inv_level_sigma2=(1.0 / (1.2 ** levels) ** 2).astype(np.float32), max_chi2=float(max_chi2),
                 fix_scale=int(bool(fix_scale)), gt_s12=np.array(gt).reshape(F, 13), outlier=cat("outlier", 1, bool),
                 n_corr=np.array(counts, np.int32))
+
+
+def make_sim3solver_batch(seed: int = 0, n_corr=(150,), outlier_frac=0.2, noise_px: float = 0.3, fix_scale: bool = False,
+                          max_iterations: int = 300, maxk: int = 300, min_inliers: int = 20, probability: float = 0.99,
+                          extras: int = 3, cam=KITTI):
+    """A batch of Sim3Solver problems in the orb_sim3solver_batch layout (loop candidates after SearchByBoW).
+
+    make_optsim3_batch's noise-free geometry (ground truth S12, two world poses, shuffled slots and the
+    `extras` slots the keep test must drop), with the error where the solver reads it: the solver never looks at
+    the keypoints, it projects the matched map points, so keyframe 2's map points are moved in its camera frame,
+    parallel to the image plane, by what shifts their projection by N(0, noise_px) pixels per axis, and a fraction
+    outlier_frac (scalar or per pair) of the correspondences by +-U(30, 80) pixels per axis instead.  Adds
+    level_sigma2 = 1.2^(2 level) in float, draws (make_draws with the same seed) and the RANSAC parameters.  Returns
+    the batch plus gt_s12, outlier (total_kp1, bool) and n_corr."""
+    from .sim3solver import make_draws
+    b = make_optsim3_batch(seed, n_corr=n_corr, n_outliers=0, noise=False, extras=extras, fix_scale=fix_scale, cam=cam)
+    rng = np.random.default_rng([seed, 77])
+    F = len(b["kp1_begin"]) - 1
+    frac = [float(outlier_frac)] * F if np.isscalar(outlier_frac) else [float(f) for f in outlier_frac]
+    xw2 = b["mp2_xw"].astype(np.float64)
+    outlier = np.zeros(len(b["match12"]), bool)
+    for p in range(F):
+        k1, k1e, k2 = int(b["kp1_begin"][p]), int(b["kp1_begin"][p + 1]), int(b["kp2_begin"][p])
+        m = b["match12"][k1:k1e]
+        keep = np.nonzero((b["mp1_valid"][k1:k1e] != 0) & (m >= 0) & (b["mp2_valid"][k2 + np.maximum(m, 0)] != 0))[0]
+        n = len(keep)
+        out = np.zeros(n, bool)
+        out[rng.permutation(n)[:int(round(frac[p] * n))]] = True
+        px = np.where(out[:, None], rng.choice([-1, 1], (n, 2)) * rng.uniform(30, 80, (n, 2)), rng.normal(0, noise_px, (n, 2)))
+        R2, t2 = b["pose2"][p][:9].reshape(3, 3).astype(np.float64), b["pose2"][p][9:].astype(np.float64)
+        rows = k2 + m[keep]
+        Xc = xw2[rows] @ R2.T + t2
+        dXc = np.stack([px[:, 0] * Xc[:, 2] / cam["fx"], px[:, 1] * Xc[:, 2] / cam["fy"], np.zeros(n)], 1)
+        xw2[rows] = xw2[rows] + dXc @ R2
+        outlier[k1 + keep] = out
+    for k in ("s12", "inv_level_sigma2", "max_chi2"):
+        del b[k]
+    b.update(mp2_xw=xw2.astype(np.float32), outlier=outlier, level_sigma2=((1.2 ** np.arange(8)) ** 2).astype(np.float32),
+             draws=np.ascontiguousarray(make_draws(F, max(max_iterations, 300), seed)[:, :max_iterations]), rand_max=2147483647, probability=float(probability),
+             min_inliers=int(min_inliers), max_iterations=int(max_iterations), maxk=int(maxk), fix_scale=int(bool(fix_scale)))
+    return b
