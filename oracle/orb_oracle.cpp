@@ -765,6 +765,29 @@ static SE3 se3_exp_mul(const double* upd, const SE3& T) {
     return out;
 }
 
+// One LM trial as oracle_local_ba_trace records it (tests/oracle_api.py BA_TRIAL_DTYPE has the same
+// layout).  The iteration-end fields are filled on the trial that closes an iteration (iter_end = 1);
+// loop_end names why the loop ended on the trial that closes its last iteration.
+struct oracle_ba_trial {
+    int32_t loop, it, q, accepted;     // loop 0 / 1, iteration, trial within the iteration (from 0)
+    double lambda, cur, tmp, scale, rho;   // lambda and cur before the trial; scale with its 1e-3
+    int32_t iter_end, nbad_tested;     // nbad_tested: the iteration reached the (ini - cur) * 1e3 < ini test
+    double ini, cur_end;
+    int32_t nbad, loop_end;            // loop_end: BA_END_*
+};
+enum { BA_END_NONE = 0, BA_END_BUDGET, BA_END_NBAD, BA_END_RHO0, BA_END_Q10, BA_END_STOP };
+
+struct BATrace {
+    oracle_ba_trial* rec = nullptr;
+    int cap = 0, n = 0, loop = 0;
+    oracle_ba_trial* push() {
+        oracle_ba_trial* r = n < cap ? &rec[n] : nullptr;
+        n++;   // counts past cap, so the caller sees an overflow
+        if (r) { std::memset(r, 0, sizeof *r); r->loop = loop; }
+        return r;
+    }
+};
+
 struct BA {
     // problem
     int P, N, E;
@@ -784,6 +807,8 @@ struct BA {
     int np = 0, nl = 0;
     const volatile int32_t* stop = nullptr;
     int stop_after = -1, trials = 0;   // test hook: the flag "rises" once this many LM trials have run
+    BATrace* trace = nullptr;          // test hook: a record per LM trial; read-only for the optimisation
+    int end_reason = BA_END_NONE;      // why the last optimize() ended (BA_END_NONE: it had nothing to do)
 
     bool terminate() const { return (stop && *stop) || (stop_after >= 0 && trials >= stop_after); }
 
@@ -1055,6 +1080,8 @@ struct BA {
         double lambda = 0, ni = 2;
         int nbad = 0, done_iters = 0;
         final_chi = 0;
+        end_reason = BA_END_NONE;
+        oracle_ba_trial* tr = nullptr;
         if (np + nl == 0 || act_edges.empty()) return 0;
         for (int it = 0; it < iters && !terminate(); it++) {
             compute_active_errors();
@@ -1065,6 +1092,8 @@ struct BA {
             double rho = 0;
             int q = 0;
             do {
+                tr = trace ? trace->push() : nullptr;
+                if (tr) { tr->it = it; tr->q = q; tr->lambda = lambda; tr->cur = cur; }
                 push();
                 const bool ok = solve(lambda);
                 update();
@@ -1078,6 +1107,7 @@ struct BA {
                 for (int j = 0; j < 3 * nl; j++) scale += x[(size_t)D + j] * (lambda * x[(size_t)D + j] + bl[j]);
                 scale += 1e-3;
                 rho /= scale;
+                if (tr) { tr->tmp = tmp; tr->scale = scale; tr->rho = rho; tr->accepted = rho > 0 && std::isfinite(tmp); }
                 if (rho > 0 && std::isfinite(tmp)) {
                     double alpha = 1. - std::pow((2 * rho - 1), 3);
                     alpha = std::min(alpha, 2. / 3.);
@@ -1094,10 +1124,16 @@ struct BA {
             } while (rho < 0 && q < 10 && !terminate());
             done_iters++;
             final_chi = cur;
-            if (q == 10 || rho == 0) break;
+            if (tr) { tr->iter_end = 1; tr->ini = ini; tr->cur_end = cur; tr->nbad = nbad; }
+            end_reason = BA_END_BUDGET;   // (until something below says otherwise)
+            if (q == 10 || rho == 0) { end_reason = q == 10 ? BA_END_Q10 : BA_END_RHO0; break; }
             if ((ini - cur) * 1e3 < ini) nbad++; else nbad = 0;
-            if (nbad >= 3) break;
+            if (tr) { tr->nbad_tested = 1; tr->nbad = nbad; }
+            if (nbad >= 3) { end_reason = BA_END_NBAD; break; }
         }
+        if (end_reason == BA_END_BUDGET && done_iters < iters) end_reason = BA_END_STOP;   // terminate() ended it
+        if (end_reason == BA_END_NONE && terminate()) end_reason = BA_END_STOP;
+        if (tr) tr->loop_end = end_reason;
         return done_iters;
     }
 };
@@ -1903,10 +1939,13 @@ int oracle_compute_stereo_matches(const orbm_stereo_view* L, const orbm_stereo_v
 
 // stop_after >= 0: the stop flag is raised right after that many LM trials (between trials, where
 // g2o polls terminate(): optimization_algorithm_levenberg.cpp:149, sparse_optimizer.cpp:376).
-int oracle_local_ba_stop_after(const orbba_problem* pr, orbba_result* res, const volatile int32_t* stop,
-                               int stop_after) {
+// trace / end_reason (either may be null): the per-trial records and why each optimize() ended.
+static int local_ba_run(const orbba_problem* pr, orbba_result* res, const volatile int32_t* stop, int stop_after,
+                        BATrace* trace, int32_t* end_reason) {
     BA ba;
     ba.stop_after = stop_after;
+    ba.trace = trace;
+    if (end_reason) end_reason[0] = end_reason[1] = BA_END_NONE;
     ba.P = pr->n_poses; ba.N = pr->n_points; ba.E = pr->n_edges;
     ba.stop = stop;
     ba.pose.resize(ba.P);
@@ -1933,6 +1972,7 @@ int oracle_local_ba_stop_after(const orbba_problem* pr, orbba_result* res, const
     if (run) {
         ba.init_level(0);
         res->iterations[0] = ba.optimize(5, res->chi2[0]);
+        if (end_reason) end_reason[0] = ba.end_reason;
         bool more = !ba.terminate();
         if (more) {
             for (int e = 0; e < ba.E; e++) {
@@ -1941,7 +1981,9 @@ int oracle_local_ba_stop_after(const orbba_problem* pr, orbba_result* res, const
                 ba.robust[e] = 0;
             }
             ba.init_level(0);
+            if (trace) trace->loop = 1;
             res->iterations[1] = ba.optimize(10, res->chi2[1]);
+            if (end_reason) end_reason[1] = ba.end_reason;
         }
     }
     for (int e = 0; e < ba.E; e++) {
@@ -1960,6 +2002,22 @@ int oracle_local_ba_stop_after(const orbba_problem* pr, orbba_result* res, const
     }
     std::memcpy(res->points, ba.X.data(), sizeof(double) * 3 * ba.N);
     return 0;
+}
+
+int oracle_local_ba_stop_after(const orbba_problem* pr, orbba_result* res, const volatile int32_t* stop,
+                               int stop_after) {
+    return local_ba_run(pr, res, stop, stop_after, nullptr, nullptr);
+}
+
+// The same run with a record per LM trial written to trace[0 .. cap) and why each optimize() ended in
+// end_reason[2] (BA_END_*).  Returns the number of trials (more than cap: the array was too short).
+int oracle_local_ba_trace(const orbba_problem* pr, orbba_result* res, const volatile int32_t* stop, int stop_after,
+                          oracle_ba_trial* trace, int cap, int32_t* end_reason) {
+    BATrace t;
+    t.rec = trace;
+    t.cap = cap;
+    local_ba_run(pr, res, stop, stop_after, &t, end_reason);
+    return t.n;
 }
 
 int oracle_local_ba(const orbba_problem* pr, orbba_result* res, const volatile int32_t* stop) {

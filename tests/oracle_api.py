@@ -257,7 +257,21 @@ def ba_problem(keep, prob):
                      keep(prob["edge_cam"], np.float64))
 
 
-def local_ba(prob, stop=None, stop_after=-1):
+# oracle_ba_trial (oracle/orb_oracle.cpp): one record per LM trial.  lambda / cur are the values before the
+# trial, scale includes its 1e-3; ini / cur_end / nbad are filled on the trial that closes an iteration
+# (iter_end), nbad after the relative-improvement test where the iteration reached it (nbad_tested);
+# loop_end indexes BA_END_REASONS on the trial that closes a loop's last iteration, else 0.
+BA_TRIAL_DTYPE = np.dtype([("loop", "<i4"), ("it", "<i4"), ("q", "<i4"), ("accepted", "<i4"), ("lambda", "<f8"),
+                           ("cur", "<f8"), ("tmp", "<f8"), ("scale", "<f8"), ("rho", "<f8"), ("iter_end", "<i4"),
+                           ("nbad_tested", "<i4"), ("ini", "<f8"), ("cur_end", "<f8"), ("nbad", "<i4"),
+                           ("loop_end", "<i4")])
+BA_END_REASONS = ("none", "budget", "nbad", "rho0", "q10", "stop")   # "none": the loop had nothing to do
+BA_MAX_TRIALS = (5 + 10) * 10
+
+
+def local_ba(prob, stop=None, stop_after=-1, trace=False):
+    """The oracle's LocalBundleAdjustment.  trace=True: the same run through oracle_local_ba_trace; the
+    result also has "trace" (BA_TRIAL_DTYPE records) and "end_reason" (a BA_END_REASONS name per loop)."""
     keep = _Keep()
     pr = ba_problem(keep, prob)
     P, N, E = pr.n_poses, pr.n_points, pr.n_edges
@@ -268,7 +282,16 @@ def local_ba(prob, stop=None, stop_after=-1):
     sf = None
     if stop is not None:
         sf = C.byref(C.c_int32(int(stop)))
-    lib().oracle_local_ba_stop_after(C.byref(pr), C.byref(res), sf, int(stop_after))
+    if trace:
+        assert BA_TRIAL_DTYPE.itemsize == 88
+        rec = np.zeros(BA_MAX_TRIALS, BA_TRIAL_DTYPE)
+        why = np.zeros(2, np.int32)
+        n = lib().oracle_local_ba_trace(C.byref(pr), C.byref(res), sf, int(stop_after), ptr(rec), len(rec), ptr(why))
+        assert 0 <= n <= len(rec), n
+        out["trace"] = rec[:n].copy()
+        out["end_reason"] = tuple(BA_END_REASONS[w] for w in why)
+    else:
+        lib().oracle_local_ba_stop_after(C.byref(pr), C.byref(res), sf, int(stop_after))
     out["iterations"] = tuple(res.iterations)
     out["chi2"] = tuple(res.chi2)
     return out
