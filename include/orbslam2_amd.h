@@ -945,6 +945,84 @@ int orb_sim3solver_iterate(const orb_sim3solver_batch* in, orb_sim3solver_result
  * the workspace).  A draw outside [0, rand_max] is clamped to a valid position.  One lane per hypothesis. */
 int orb_sim3solver_iterate_device(const orb_sim3solver_batch* in, orb_sim3solver_result* out, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * PnPsolver(Frame, matches), SetRansacParameters(probability, minInliers, maxIterations, minSet, epsilon, th2)
+ * and cv::Mat PnPsolver::iterate(int nIterations, bool& bNoMore, vector<bool>& vbInliers, int& nInliers)
+ * (include/PnPsolver.h, src/PnPsolver.cc; Tracking::Relocalization, Tracking.cc:336-362: 0.99, 10, 300, 4, 0.5f,
+ * 5.991f, iterate(5)), batched over candidate keyframes: one solver per frame slot range, in the layout of
+ * orbm_reloc_batch / orbba_pose_batch, so orbm_search_by_bow_batch_device's matches feed in (as mp_valid, mp_xw)
+ * and tcw / inlier feed orbba_pose_optimization_device.
+ * Correspondences (:79-101): the slots i with mp_valid[i], ascending; P2D = kp_xy[i], P3Dw = mp_xw[i],
+ * maxError = level_sigma2[octave] * th2, all float.  N is their count.
+ * SetRansacParameters (:121-157): minInliers = max(int(N * epsilon), min_inliers, min_set), eps = max(epsilon,
+ * (float)minInliers / N), cap = 1 when minInliers == N, else ceil(log(1 - probability) / log(1 - pow(eps, 3)))
+ * in double, clamped to [1, max_iterations] (compared in double before narrowing).  The host computes cap for
+ * every N in 0 .. ORBM_PROJ_MAX_KP with libm and the kernel indexes that table.
+ * Draws (:191-201): hypothesis k of candidate p uses draws[p, k, 0..3], raw rand() values in [0, rand_max]; draw
+ * c picks position int(((double)r / ((double)rand_max + 1.0)) * (N - c)) of the available indices, which is then
+ * refilled from the back and popped.  A result does not depend on how the iterations are split over calls.
+ * Hypothesis: EPnP (compute_pose, :477-526) in fp64 on the four correspondences, then CheckInliers (:308-339)
+ * with the reference's mix of float and double and the strict float <.  Where the reference reads an OpenCV SVD
+ * whose rounding decides the answer, a rule of the data stands instead (PnPsolver).
+ * Control (:165-258), per candidate, on the state (iterations, best_inliers, best_mask, best_tcw) that the call
+ * reads and writes.  N < minInliers: terminate = 1, found = 0, the state unchanged.  Otherwise k runs over
+ * [iterations, max(cap, iterations + maxk)) -- the reference's loop condition is an OR, so a fresh solver runs
+ * its whole cap in one call and an exhausted one maxk more.  A hypothesis with n[k] >= minInliers replaces the
+ * best when n[k] > best_inliers, and then Refine() (EPnP over the best inliers, CheckInliers) succeeds when its
+ * count is > minInliers: found = 1, tcw / inlier / n_inliers are the refined ones, iterations = k + 1.  Without a
+ * success iterations = the end of the range, terminate = (iterations >= cap), and with terminate and
+ * best_inliers >= minInliers found = 2 and tcw / inlier / n_inliers are the best (unrefined) ones.  Otherwise
+ * found = 0 and tcw, inlier and n_inliers are 0 (nothing is left unwritten). */
+typedef struct orb_pnpsolver_batch {
+    int32_t        n_frames, total_kp;
+    const int32_t* kp_begin;     /* n_frames + 1 */
+    const float*   kp_xy;        /* total_kp x 2: keypointsUn */
+    const int32_t* kp_octave;    /* total_kp */
+    const float*   camera;       /* n_frames x 4: fx, fy, cx, cy */
+    const uint8_t* mp_valid;     /* total_kp: vpMapPointMatches[i] && !isBad() */
+    const float*   mp_xw;        /* total_kp x 3 */
+    int32_t        n_levels;
+    const float*   level_sigma2; /* host, n_levels (pyramid.sigmaSq) */
+    const int32_t* draws;        /* n_frames x n_draws x 4: rand() values in [0, rand_max] */
+    int32_t        n_draws;      /* >= the end of the range of every candidate */
+    int32_t        rand_max;     /* RAND_MAX of the generator that made draws (glibc: 2147483647) */
+    double         probability;  /* in (0, 1) */
+    int32_t        min_inliers;  /* >= 6 (a departure: Refine on five points has a two-dimensional null space) */
+    int32_t        max_iterations; /* >= 1 */
+    int32_t        min_set;      /* 4 */
+    float          epsilon;      /* in [0, 1] */
+    float          th2;          /* > 0 */
+    int32_t        maxk;         /* iterate(nIterations); >= 1 */
+} orb_pnpsolver_batch;
+
+typedef struct orb_pnpsolver_result {
+    float*   tcw;          /* n_frames x 12: Rcw (row-major 3x3) then tcw, 0 when nothing is returned */
+    uint8_t* inlier;       /* total_kp: vbInliers, in keypoint slots */
+    int32_t* found;        /* n_frames: 1 refined, 2 best at termination, 0 none; -1 from the device entry for a
+                            * candidate with more than ORBM_PROJ_MAX_KP keypoints or whose range would pass
+                            * n_draws (its state unchanged, terminate 1, the other outputs 0) */
+    int32_t* n_inliers;    /* n_frames: nInliers */
+    int32_t* terminate;    /* n_frames: bNoMore */
+    int32_t* iterations;   /* n_frames, in / out: mnIterations (0 for a fresh solver) */
+    int32_t* best_inliers; /* n_frames, in / out: mnBestInliers (0 for a fresh solver) */
+    uint8_t* best_mask;    /* total_kp, in / out: mvbBestInliers in keypoint slots */
+    float*   best_tcw;     /* n_frames x 12, in / out: mBestTcw */
+    int32_t* hyp_inliers;  /* n_frames x n_draws: n[k] of the hypotheses the reference would have evaluated in
+                            * this call, -1 elsewhere; may be NULL */
+} orb_pnpsolver_result;
+
+/* Host entry: every pointer is host memory, synchronous; offsets, octaves, the state, the length of the draw
+ * table and draws in [0, rand_max] are validated before anything is copied; a frame with more than
+ * ORBM_PROJ_MAX_KP keypoints is refused. */
+int orb_pnpsolver_iterate(const orb_pnpsolver_batch* in, orb_pnpsolver_result* out, int device);
+/* Device entry: every array in HBM except level_sigma2; enqueues only on `stream` (the first call with a new
+ * parameter set uploads its cap table synchronously, as the first call allocates the workspace).  A draw outside
+ * [0, rand_max] is clamped to a valid position.  One lane per hypothesis, one wavefront per Refine().
+ * The workspace (records, ranges, hypothesis poses) is one per host thread and shared by every stream that
+ * thread enqueues on: two calls from one thread on different streams need an event or a synchronise between
+ * them, as with orb_sim3solver_iterate_device. */
+int orb_pnpsolver_iterate_device(const orb_pnpsolver_batch* in, orb_pnpsolver_result* out, void* stream);
+
 const char* orb_last_error(void);
 int orb_device_count(void);
 

@@ -520,6 +520,43 @@ struct Sim3Solver {
     }
 };
 
+// PnPsolver (include/PnPsolver.h, src/PnPsolver.cc): the EPnP RANSAC of Tracking::Relocalization between SearchByBoW
+// and PoseOptimization, a solver per candidate keyframe in the slot layout of orb_pnpsolver_batch (mp_valid / mp_xw
+// are SearchByBoW's matches, draws the rand() values of every hypothesis, r.iterations / r.best_inliers / r.best_mask /
+// r.best_tcw the solvers' state, read and written).  The constructor takes the arrays, SetRansacParameters the
+// reference's six parameters (Tracking.cc:352: 0.99, 10, 300, 4, 0.5f, 5.991f), iterate / find run the batch.
+class PnPsolver {
+public:
+    PnPsolver(int32_t n_frames, int32_t total_kp, const int32_t* kp_begin, const float* kp_xy, const int32_t* kp_octave,
+              const float* camera, const uint8_t* mp_valid, const float* mp_xw, int32_t n_levels, const float* level_sigma2,
+              const int32_t* draws, int32_t n_draws, int32_t rand_max = 2147483647)
+        : b_{n_frames, total_kp, kp_begin, kp_xy, kp_octave, camera, mp_valid, mp_xw, n_levels, level_sigma2, draws, n_draws,
+             rand_max, 0.99, 8, 300, 4, 0.4f, 5.991f, 1} {}   // the defaults of PnPsolver.h's SetRansacParameters
+    void SetRansacParameters(double probability = 0.99, int minInliers = 8, int maxIterations = 300, int minSet = 4,
+                             float epsilon = 0.4f, float th2 = 5.991f) {
+        b_.probability = probability; b_.min_inliers = minInliers; b_.max_iterations = maxIterations;
+        b_.min_set = minSet; b_.epsilon = epsilon; b_.th2 = th2;
+    }
+    // cv::Mat iterate(nIterations, bNoMore, vbInliers, nInliers) of every candidate's solver on HBM arrays.  Enqueue
+    // only: r.found = 1 (refined) / 2 (best at termination) / 0, r.tcw the pose, r.inlier vbInliers, r.terminate bNoMore.
+    void IterateBatch(int nIterations, orb_pnpsolver_result& r, void* stream = nullptr) {
+        b_.maxk = nIterations;
+        check(orb_pnpsolver_iterate_device(&b_, &r, stream), "orb_pnpsolver_iterate_device");
+    }
+    // The same on host arrays, synchronous.
+    void iterate(int nIterations, orb_pnpsolver_result& r, int device = 0) {
+        b_.maxk = nIterations;
+        check(orb_pnpsolver_iterate(&b_, &r, device), "orb_pnpsolver_iterate");
+    }
+    // cv::Mat find(vbInliers, nInliers): iterate(maxIterations) (:159-163; the reference passes the adjusted cap,
+    // which the OR rule makes the same range for a fresh solver).
+    void find(orb_pnpsolver_result& r, int device = 0) { iterate(b_.max_iterations, r, device); }
+    const orb_pnpsolver_batch& batch() const { return b_; }
+
+private:
+    orb_pnpsolver_batch b_;
+};
+
 // void MapPoint::ComputeDistinctiveDescriptors() (src/MapPoint.cc:257-320), batched over map points on HBM
 // arrays: point p holds the rows [begin[p], begin[p + 1]) of d_desc.  Enqueue only; best[p] = the winning
 // point-relative row (-1: empty), d_out_desc[p] = that row (an empty point's row is not written, so

@@ -181,6 +181,23 @@ class Sim3SolverResult(C.Structure):
                 ("terminate", C.c_void_p), ("hyp_inliers", C.c_void_p)]
 
 
+class PnPSolverBatch(C.Structure):
+    """orb_pnpsolver_batch (include/orbslam2_amd.h)."""
+    _fields_ = [("n_frames", C.c_int32), ("total_kp", C.c_int32), ("kp_begin", C.c_void_p), ("kp_xy", C.c_void_p),
+                ("kp_octave", C.c_void_p), ("camera", C.c_void_p), ("mp_valid", C.c_void_p), ("mp_xw", C.c_void_p),
+                ("n_levels", C.c_int32), ("level_sigma2", C.c_void_p), ("draws", C.c_void_p), ("n_draws", C.c_int32),
+                ("rand_max", C.c_int32), ("probability", C.c_double), ("min_inliers", C.c_int32),
+                ("max_iterations", C.c_int32), ("min_set", C.c_int32), ("epsilon", C.c_float), ("th2", C.c_float),
+                ("maxk", C.c_int32)]
+
+
+class PnPSolverResult(C.Structure):
+    """orb_pnpsolver_result (include/orbslam2_amd.h)."""
+    _fields_ = [("tcw", C.c_void_p), ("inlier", C.c_void_p), ("found", C.c_void_p), ("n_inliers", C.c_void_p),
+                ("terminate", C.c_void_p), ("iterations", C.c_void_p), ("best_inliers", C.c_void_p),
+                ("best_mask", C.c_void_p), ("best_tcw", C.c_void_p), ("hyp_inliers", C.c_void_p)]
+
+
 # cv::KeyPoint layout (28 bytes)
 KP_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("size", "<f4"), ("angle", "<f4"),
                      ("response", "<f4"), ("octave", "<i4"), ("class_id", "<i4")])
@@ -252,6 +269,8 @@ SIGNATURES = {
     "orbba_optimize_sim3_device": (C.c_int, [C.POINTER(OptSim3Batch), C.POINTER(OptSim3Result), VP]),
     "orb_sim3solver_iterate": (C.c_int, [C.POINTER(Sim3SolverBatch), C.POINTER(Sim3SolverResult), C.c_int]),
     "orb_sim3solver_iterate_device": (C.c_int, [C.POINTER(Sim3SolverBatch), C.POINTER(Sim3SolverResult), VP]),
+    "orb_pnpsolver_iterate": (C.c_int, [C.POINTER(PnPSolverBatch), C.POINTER(PnPSolverResult), C.c_int]),
+    "orb_pnpsolver_iterate_device": (C.c_int, [C.POINTER(PnPSolverBatch), C.POINTER(PnPSolverResult), VP]),
     "orbx_pack_descriptors": (C.c_int,[VP, C.c_int, VP, VP, C.c_int, VP, C.c_int, VP]),
     "orbx_profile_enable": (C.c_int, [VP, C.c_int]),
     "orbx_profile_read": (C.c_int, [VP, VP, VP]),

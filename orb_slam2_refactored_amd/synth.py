@@ -1116,3 +1116,56 @@ def make_sim3solver_batch(seed: int = 0, n_corr=(150,), outlier_frac=0.2, noise_
              draws=np.ascontiguousarray(make_draws(F, max(max_iterations, 300), seed)[:, :max_iterations]), rand_max=2147483647, probability=float(probability),
              min_inliers=int(min_inliers), max_iterations=int(max_iterations), maxk=int(maxk), fix_scale=int(bool(fix_scale)))
     return b
+
+
+def make_pnp_batch(seed: int = 0, n_corr=(150,), outlier_frac=0.2, noise_px: float = 0.3, extras_frac: float = 0.25,
+                   n_draws: int = 300, probability: float = 0.99, min_inliers: int = 10, max_iterations: int = 300,
+                   epsilon: float = 0.5, th2: float = 5.991, maxk: int = 5, cam=KITTI):
+    """A batch of PnPsolver problems in the orb_pnpsolver_batch layout (relocalisation candidates after SearchByBoW).
+
+    Per candidate a ground-truth Tcw (a rotation of up to 20 degrees about a random axis, a translation of a few
+    metres) and n_corr[p] map points seen at a uniform pixel with a depth uniform in [4, 30] m: the depth spread is
+    of the order of the depth, so no scene is planar.  The keypoint is the projection plus N(0, noise_px) per axis,
+    or for a fraction outlier_frac (scalar or per candidate) of the correspondences plus +-U(30, 80) pixels per
+    axis.  About extras_frac * n_corr unmatched slots (mp_valid = 0, arbitrary keypoint and point) are interleaved
+    at random positions, so the compaction is exercised.  Octaves are uniform in 0 .. 7, level_sigma2 = 1.2^(2
+    level).  Returns the batch (with draws from pnpsolver.make_draws and the RANSAC parameters) plus gt_tcw (F, 12),
+    outlier (total_kp, bool) and n_corr."""
+    from .pnpsolver import make_draws
+    rng = np.random.default_rng([seed, 4177])
+    counts = [int(n) for n in n_corr]
+    F = len(counts)
+    frac = [float(outlier_frac)] * F if np.isscalar(outlier_frac) else [float(f) for f in outlier_frac]
+    begin, xy, octs, valid, xw, outl, gts = [0], [], [], [], [], [], []
+    for p, n in enumerate(counts):
+        axis = rng.normal(size=3)
+        axis /= np.linalg.norm(axis)
+        ang = np.deg2rad(rng.uniform(2, 20))
+        Kx = np.array([[0, -axis[2], axis[1]], [axis[2], 0, -axis[0]], [-axis[1], axis[0], 0]])
+        R = np.eye(3) + np.sin(ang) * Kx + (1 - np.cos(ang)) * Kx @ Kx
+        t = rng.uniform(-3, 3, 3)
+        n_extra = int(round(extras_frac * n)) + (1 if n == 0 else 0)
+        tot = n + n_extra
+        is_corr = np.zeros(tot, bool)
+        is_corr[rng.permutation(tot)[:n]] = True
+        px = np.stack([rng.uniform(20, cam["width"] - 20, tot), rng.uniform(20, cam["height"] - 20, tot)], 1)
+        z = rng.uniform(4, 30, tot)
+        Xc = np.stack([(px[:, 0] - cam["cx"]) * z / cam["fx"], (px[:, 1] - cam["cy"]) * z / cam["fy"], z], 1)
+        Xw = (Xc - t) @ R   # R^T (Xc - t)
+        out = np.zeros(tot, bool)
+        ci = np.nonzero(is_corr)[0]
+        out[ci[rng.permutation(n)[:int(round(frac[p] * n))]]] = True
+        d = np.where(out[:, None], rng.choice([-1, 1], (tot, 2)) * rng.uniform(30, 80, (tot, 2)), rng.normal(0, noise_px, (tot, 2)))
+        kp = px + d
+        kp[~is_corr] = np.stack([rng.uniform(0, cam["width"], tot), rng.uniform(0, cam["height"], tot)], 1)[~is_corr]
+        begin.append(begin[-1] + tot)
+        xy.append(kp); octs.append(rng.integers(0, 8, tot)); valid.append(is_corr); xw.append(Xw); outl.append(out & is_corr)
+        gts.append(np.concatenate([R.reshape(9), t]))
+    cat = lambda parts, w, dt: (np.concatenate(parts) if parts else np.zeros((0, w))).astype(dt).reshape((-1, w) if w > 1 else (-1,))   # noqa: E731
+    return dict(kp_begin=np.array(begin, np.int32), kp_xy=cat(xy, 2, np.float32), kp_octave=cat(octs, 1, np.int32),
+                camera=np.tile(np.array([cam["fx"], cam["fy"], cam["cx"], cam["cy"]], np.float32), (F, 1)),
+                mp_valid=cat(valid, 1, np.uint8), mp_xw=cat(xw, 3, np.float32),
+                level_sigma2=((1.2 ** np.arange(8)) ** 2).astype(np.float32), draws=make_draws(F, n_draws, seed),
+                rand_max=2147483647, probability=float(probability), min_inliers=int(min_inliers), max_iterations=int(max_iterations),
+                min_set=4, epsilon=float(epsilon), th2=float(th2), maxk=int(maxk), gt_tcw=np.array(gts, np.float32).reshape(F, 12),
+                outlier=cat(outl, 1, bool), n_corr=np.array(counts, np.int32))
