@@ -1023,6 +1023,73 @@ int orb_pnpsolver_iterate(const orb_pnpsolver_batch* in, orb_pnpsolver_result* o
  * them, as with orb_sim3solver_iterate_device. */
 int orb_pnpsolver_iterate_device(const orb_pnpsolver_batch* in, orb_pnpsolver_result* out, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Initializer(ReferenceFrame, sigma, iterations) and bool Initializer::Initialize(CurrentFrame, vMatches12, R21,
+ * t21, vP3D, vbTriangulated) (include/Initializer.h, src/Initializer.cc:45-122; Tracking::MonocularInitialization,
+ * Tracking.cc:1033-1075), batched over (reference frame, current frame) pairs: frame 1 of pair p holds the slots
+ * [kp1_begin[p], kp1_begin[p+1]) of kp1_xy (keypointsUn), frame 2 likewise, and matches12 is what
+ * orbm_search_for_initialization* writes (the frame-2-relative index of slot i's match, -1 for none).
+ * mvMatches12 (:55-64): the slots with matches12[i] >= 0, ascending; N is their count.  Normalize (:750-796) runs
+ * over all keypoints of either frame in float (summation order: csrc/orbinit.hip).
+ * Draws (:83-98): hypothesis `it` of pair p uses draws[p, it, 0..7], raw rand() values in [0, rand_max]; draw j
+ * picks position int(((double)r / ((double)rand_max + 1.0)) * (N - j)) of the available indices, which is then
+ * refilled from the back and popped.  The same eight indices serve the homography and the fundamental matrix.
+ * Hypotheses: ComputeH21 / ComputeF21 (:227-304) under rules of the data in fp64 (csrc/init_hyp.h, DESIGN.md
+ * section 4, Initializer), H21i / H12i / F21i rounded to float; CheckHomography / CheckFundamental (:306-469) in
+ * the reference's float expressions and summation order.  The winner of either model is the first maximum of the
+ * scores (currentScore > score from 0); a model none of whose scores is positive has best = -1, a zero matrix and
+ * an empty mask.  RH = SH / (SH + SF) in float picks ReconstructH (RH > rh_threshold) or ReconstructF (:113-119).
+ * ReconstructF (:471-571) tries (R1, t), (R2, t), (R1, -t), (R2, -t) of DecomposeE, ReconstructH (:573-733)
+ * Faugeras' eight hypotheses, each through CheckRT (:799-908) with the reference's tests and types; the decision
+ * rules are the reference's.  Departures: N < 8 evaluates nothing (found = 0; the reference would draw from an
+ * empty vector); parallax is the element of rank min(50, nGood - 1) with ties broken by correspondence index. */
+typedef struct orb_initializer_batch {
+    int32_t        n_pairs, total_kp1, total_kp2;
+    const int32_t* kp1_begin;    /* n_pairs + 1 */
+    const int32_t* kp2_begin;    /* n_pairs + 1 */
+    const float*   kp1_xy;       /* total_kp1 x 2: the reference frame's keypointsUn */
+    const float*   kp2_xy;       /* total_kp2 x 2: the current frame's keypointsUn */
+    const int32_t* matches12;    /* total_kp1 */
+    const float*   camera;       /* n_pairs x 4: fx, fy, cx, cy */
+    const int32_t* draws;        /* n_pairs x max_iterations x 8: rand() values in [0, rand_max] */
+    int32_t        rand_max;     /* RAND_MAX of the generator that made draws (glibc: 2147483647) */
+    float          sigma;        /* > 0 (1.0) */
+    int32_t        max_iterations; /* >= 1 (200) */
+    float          min_parallax; /* degrees (1.0) */
+    int32_t        min_triangulated; /* (50) */
+    double         rh_threshold; /* (0.40) */
+} orb_initializer_batch;
+
+typedef struct orb_initializer_result {
+    int32_t* found;        /* n_pairs: 1 initialised, 0 not; -1 from the device entry for a pair either of whose
+                            * frames has more than ORBM_PROJ_MAX_KP keypoints (every other output of the pair 0) */
+    int32_t* model;        /* n_pairs: 0 = ReconstructH, 1 = ReconstructF was tried */
+    float*   r21t21;       /* n_pairs x 12: R21 (row-major 3x3) then t21; 0 without a success */
+    float*   p3d;          /* total_kp1 x 3: vP3D in reference-frame keypoint slots; 0 without a success */
+    uint8_t* triangulated; /* total_kp1: vbTriangulated */
+    float*   score_h;      /* n_pairs: SH */
+    float*   score_f;      /* n_pairs: SF */
+    int32_t* best_h;       /* n_pairs: the winning `it` of FindHomography, -1 for none */
+    int32_t* best_f;       /* n_pairs: of FindFundamental */
+    float*   h21;          /* n_pairs x 9 */
+    float*   f21;          /* n_pairs x 9 */
+    uint8_t* inlier_h;     /* total_kp1: vbMatchesInliersH in keypoint slots */
+    uint8_t* inlier_f;     /* total_kp1: vbMatchesInliersF */
+    float*   hyp_score;    /* n_pairs x 2 x max_iterations: currentScore of every hypothesis, H then F */
+    int32_t* n_good;       /* n_pairs x 8: nGood of every motion hypothesis (4..7 are 0 on the F path) */
+    float*   parallax;     /* n_pairs x 8: its parallax in degrees */
+} orb_initializer_result;
+
+/* Host entry: every pointer is host memory, synchronous; offsets, matches12 in [-1, keypoints of frame 2), draws in
+ * [0, rand_max] and the scalars are validated before anything is copied; a frame with more than ORBM_PROJ_MAX_KP
+ * keypoints is refused. */
+int orb_initializer_initialize(const orb_initializer_batch* in, orb_initializer_result* out, int device);
+/* Device entry: every array in HBM; enqueues only on `stream` (the first call allocates the workspace).  A draw
+ * outside [0, rand_max] is clamped to a valid position and a match outside frame 2 is ignored.  One lane per
+ * hypothesis.  The workspace is one per host thread and shared by every stream that thread enqueues on, as with
+ * orb_pnpsolver_iterate_device. */
+int orb_initializer_initialize_device(const orb_initializer_batch* in, orb_initializer_result* out, void* stream);
+
 const char* orb_last_error(void);
 int orb_device_count(void);
 

@@ -557,6 +557,41 @@ private:
     orb_pnpsolver_batch b_;
 };
 
+// Initializer (include/Initializer.h, src/Initializer.cc): the H / F RANSAC and reconstruction of
+// Tracking::MonocularInitialization, an initializer per (reference frame, current frame) pair in the slot layout of
+// orb_initializer_batch.  The constructor takes the reference frames (their keypointsUn and cameras), sigma and the
+// iterations, as Initializer(ReferenceFrame, sigma, iterations) does; Initialize takes the current frames and
+// vMatches12 (what SearchForInitializationBatch wrote) and the rand() table.
+class Initializer {
+public:
+    Initializer(int32_t n_pairs, int32_t total_kp1, const int32_t* kp1_begin, const float* kp1_xy, const float* camera,
+                float sigma = 1.0f, int iterations = 200)
+        : b_{n_pairs, total_kp1, 0, kp1_begin, nullptr, kp1_xy, nullptr, nullptr, camera, nullptr, 2147483647, sigma, iterations,
+             1.0f, 50, 0.40} {}
+    // bool Initialize(CurrentFrame, vMatches12, R21, t21, vP3D, vbTriangulated) of every pair on HBM arrays.  Enqueue
+    // only: r.found = the return values, r.r21t21 R21 and t21, r.p3d vP3D, r.triangulated vbTriangulated.
+    void InitializeBatch(int32_t total_kp2, const int32_t* kp2_begin, const float* kp2_xy, const int32_t* matches12,
+                         const int32_t* draws, orb_initializer_result& r, void* stream = nullptr, int32_t rand_max = 2147483647) {
+        set(total_kp2, kp2_begin, kp2_xy, matches12, draws, rand_max);
+        check(orb_initializer_initialize_device(&b_, &r, stream), "orb_initializer_initialize_device");
+    }
+    // The same on host arrays, synchronous.
+    void Initialize(int32_t total_kp2, const int32_t* kp2_begin, const float* kp2_xy, const int32_t* matches12,
+                    const int32_t* draws, orb_initializer_result& r, int device = 0, int32_t rand_max = 2147483647) {
+        set(total_kp2, kp2_begin, kp2_xy, matches12, draws, rand_max);
+        check(orb_initializer_initialize(&b_, &r, device), "orb_initializer_initialize");
+    }
+    const orb_initializer_batch& batch() const { return b_; }
+
+private:
+    void set(int32_t total_kp2, const int32_t* kp2_begin, const float* kp2_xy, const int32_t* matches12, const int32_t* draws,
+             int32_t rand_max) {
+        b_.total_kp2 = total_kp2; b_.kp2_begin = kp2_begin; b_.kp2_xy = kp2_xy; b_.matches12 = matches12;
+        b_.draws = draws; b_.rand_max = rand_max;
+    }
+    orb_initializer_batch b_;
+};
+
 // void MapPoint::ComputeDistinctiveDescriptors() (src/MapPoint.cc:257-320), batched over map points on HBM
 // arrays: point p holds the rows [begin[p], begin[p + 1]) of d_desc.  Enqueue only; best[p] = the winning
 // point-relative row (-1: empty), d_out_desc[p] = that row (an empty point's row is not written, so

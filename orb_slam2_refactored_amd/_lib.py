@@ -198,6 +198,23 @@ class PnPSolverResult(C.Structure):
                 ("best_mask", C.c_void_p), ("best_tcw", C.c_void_p), ("hyp_inliers", C.c_void_p)]
 
 
+class InitializerBatch(C.Structure):
+    """orb_initializer_batch (include/orbslam2_amd.h)."""
+    _fields_ = [("n_pairs", C.c_int32), ("total_kp1", C.c_int32), ("total_kp2", C.c_int32),
+                ("kp1_begin", C.c_void_p), ("kp2_begin", C.c_void_p), ("kp1_xy", C.c_void_p), ("kp2_xy", C.c_void_p),
+                ("matches12", C.c_void_p), ("camera", C.c_void_p), ("draws", C.c_void_p), ("rand_max", C.c_int32),
+                ("sigma", C.c_float), ("max_iterations", C.c_int32), ("min_parallax", C.c_float),
+                ("min_triangulated", C.c_int32), ("rh_threshold", C.c_double)]
+
+
+class InitializerResult(C.Structure):
+    """orb_initializer_result (include/orbslam2_amd.h)."""
+    _fields_ = [("found", C.c_void_p), ("model", C.c_void_p), ("r21t21", C.c_void_p), ("p3d", C.c_void_p),
+                ("triangulated", C.c_void_p), ("score_h", C.c_void_p), ("score_f", C.c_void_p), ("best_h", C.c_void_p),
+                ("best_f", C.c_void_p), ("h21", C.c_void_p), ("f21", C.c_void_p), ("inlier_h", C.c_void_p),
+                ("inlier_f", C.c_void_p), ("hyp_score", C.c_void_p), ("n_good", C.c_void_p), ("parallax", C.c_void_p)]
+
+
 # cv::KeyPoint layout (28 bytes)
 KP_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("size", "<f4"), ("angle", "<f4"),
                      ("response", "<f4"), ("octave", "<i4"), ("class_id", "<i4")])
@@ -271,6 +288,8 @@ SIGNATURES = {
     "orb_sim3solver_iterate_device": (C.c_int, [C.POINTER(Sim3SolverBatch), C.POINTER(Sim3SolverResult), VP]),
     "orb_pnpsolver_iterate": (C.c_int, [C.POINTER(PnPSolverBatch), C.POINTER(PnPSolverResult), C.c_int]),
     "orb_pnpsolver_iterate_device": (C.c_int, [C.POINTER(PnPSolverBatch), C.POINTER(PnPSolverResult), VP]),
+    "orb_initializer_initialize": (C.c_int, [C.POINTER(InitializerBatch), C.POINTER(InitializerResult), C.c_int]),
+    "orb_initializer_initialize_device": (C.c_int, [C.POINTER(InitializerBatch), C.POINTER(InitializerResult), VP]),
     "orbx_pack_descriptors": (C.c_int,[VP, C.c_int, VP, VP, C.c_int, VP, C.c_int, VP]),
     "orbx_profile_enable": (C.c_int, [VP, C.c_int]),
     "orbx_profile_read": (C.c_int, [VP, VP, VP]),

@@ -1169,3 +1169,69 @@ def make_pnp_batch(seed: int = 0, n_corr=(150,), outlier_frac=0.2, noise_px: flo
                 rand_max=2147483647, probability=float(probability), min_inliers=int(min_inliers), max_iterations=int(max_iterations),
                 min_set=4, epsilon=float(epsilon), th2=float(th2), maxk=int(maxk), gt_tcw=np.array(gts, np.float32).reshape(F, 12),
                 outlier=cat(outl, 1, bool), n_corr=np.array(counts, np.int32))
+
+
+def make_initializer_batch(seed: int = 0, n_corr=(150,), scene=("general",), outlier_frac=0.2, noise: float = 0.3,
+                           max_iterations: int = 200, kp1_override=None):
+    """Initializer inputs (orb_initializer_batch, host arrays) shaped like Tracking::MonocularInitialization: per pair
+    N matched keypoints seen from two cameras (fx = fy = 500, a 640 x 480 image), `noise` px of Gaussian noise, a
+    fraction `outlier_frac` (scalar or per pair) of the matches pointing at an unrelated keypoint, and int(1.3 N) + 5
+    keypoints in either frame, so slots and compacted indices differ and Normalize sees unmatched points.  scene
+    (per pair): "plane" (points on a tilted plane), "general" (depths 2 to 8) or "rotation" (no translation).
+    kp1_override: {pair: keypoints in frame 1}, to build an oversized frame.  Also returns gt_r21t21 (F, 12)."""
+    from .initializer import make_draws
+    rng = np.random.default_rng(seed)
+    F = len(n_corr)
+    scenes = [scene[p % len(scene)] for p in range(F)]
+    fracs = [float(outlier_frac)] * F if np.isscalar(outlier_frac) else [float(v) for v in outlier_frac]
+    fx = fy = 500.0
+    cx, cy = 320.0, 240.0
+    b1, b2, xy1s, xy2s, m12s, gts = [0], [0], [], [], [], []
+    for p in range(F):
+        N = int(n_corr[p])
+        n1 = int(1.3 * N) + 5
+        if kp1_override and p in kp1_override:
+            n1 = int(kp1_override[p])
+        n2 = int(1.3 * N) + 5
+        u = rng.uniform(40, 600, N)
+        v = rng.uniform(40, 440, N)
+        xn, yn = (u - cx) / fx, (v - cy) / fy
+        if scenes[p] == "plane":
+            z = 4.0 / (1.0 + 0.25 * xn + 0.15 * yn)
+        else:
+            z = rng.uniform(2.0, 8.0, N)
+        X = np.stack([xn * z, yn * z, z], 1)
+        w = rng.normal(0, 1, 3)
+        w *= np.deg2rad(rng.uniform(2, 5)) / np.linalg.norm(w)
+        th = np.linalg.norm(w)
+        kx = np.array([[0, -w[2], w[1]], [w[2], 0, -w[0]], [-w[1], w[0], 0]]) / th
+        R = np.eye(3) + np.sin(th) * kx + (1 - np.cos(th)) * (kx @ kx)
+        t = np.zeros(3) if scenes[p] == "rotation" else np.array([0.45, 0.08, 0.05]) * rng.uniform(0.8, 1.2)
+        X2 = X @ R.T + t
+        p1 = np.stack([u, v], 1) + rng.normal(0, noise, (N, 2))
+        p2 = np.stack([fx * X2[:, 0] / X2[:, 2] + cx, fy * X2[:, 1] / X2[:, 2] + cy], 1) + rng.normal(0, noise, (N, 2))
+        xy1 = np.stack([rng.uniform(0, 640, n1), rng.uniform(0, 480, n1)], 1)
+        xy2 = np.stack([rng.uniform(0, 640, n2), rng.uniform(0, 480, n2)], 1)
+        s1 = np.sort(rng.choice(n1, N, replace=False))
+        s2 = rng.permutation(n2)[:N]
+        xy1[s1] = p1
+        xy2[s2] = p2
+        m12 = np.full(n1, -1, np.int32)
+        m12[s1] = s2
+        free = np.setdiff1d(np.arange(n2), s2)
+        bad = rng.random(N) < fracs[p]
+        if N and len(free):
+            m12[s1[bad]] = rng.choice(free, int(bad.sum()))
+        xy1s.append(xy1)
+        xy2s.append(xy2)
+        m12s.append(m12)
+        nt = np.linalg.norm(t)
+        gts.append(np.concatenate([R.reshape(9), t / nt if nt > 0 else t]))
+        b1.append(b1[-1] + n1)
+        b2.append(b2[-1] + n2)
+    return dict(kp1_begin=np.array(b1, np.int32), kp2_begin=np.array(b2, np.int32),
+                kp1_xy=np.concatenate(xy1s).astype(np.float32).reshape(-1, 2),
+                kp2_xy=np.concatenate(xy2s).astype(np.float32).reshape(-1, 2), matches12=np.concatenate(m12s).astype(np.int32),
+                camera=np.tile(np.array([fx, fy, cx, cy], np.float32), (F, 1)), draws=make_draws(F, max_iterations, seed),
+                rand_max=2147483647, sigma=1.0, max_iterations=int(max_iterations), min_parallax=1.0, min_triangulated=50,
+                rh_threshold=0.40, gt_r21t21=np.array(gts, np.float32).reshape(F, 12))
