@@ -201,8 +201,9 @@ int orbm_search_for_triangulation(const orbm_tri_frame* kf1, const orbm_tri_fram
                                   int32_t* match12, int32_t* nmatches);
 
 /* Batched SearchForTriangulation on HBM-resident extractor output (orbx_extract_batch_device slots),
- * e.g. the neighbour-keyframe loop of LocalMapping::CreateNewMapPoints (LocalMapping.cc:380-430)
- * issued as one launch.  Pair p matches keyframe frame1[p] of set 1 (slots at kps1 / desc1 +
+ * e.g. one round of the neighbour-keyframe loop of LocalMapping::CreateNewMapPoints
+ * (LocalMapping.cc:380-430; the loop itself, which is sequential through keyframe 1's MapPoint flags, is
+ * orblm_create_new_map_points_device).  Pair p matches keyframe frame1[p] of set 1 (slots at kps1 / desc1 +
  * frame*cap1, counts1[frame]) against frame2[p] of set 2 (NULL index arrays: p).  Sets 1 and 2 may
  * be the same arrays.  Per pair: F12 (9 floats, row-major, from ComputeF12 :55-71) and ep2 (2
  * floats, kf1's camera centre projected by kf2, :772-773; may be non-finite).  uright / has_mappoint
@@ -1089,6 +1090,117 @@ int orb_initializer_initialize(const orb_initializer_batch* in, orb_initializer_
  * hypothesis.  The workspace is one per host thread and shared by every stream that thread enqueues on, as with
  * orb_pnpsolver_iterate_device. */
 int orb_initializer_initialize_device(const orb_initializer_batch* in, orb_initializer_result* out, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * LocalMapping::CreateNewMapPoints (src/LocalMapping.cc:380-578) on extractor slots, batched over
+ * (keyframe 1, keyframe 2) pairs.  Three steps, each with a device and a host form:
+ *   orblm_prepare_pairs           per pair: Ow1, Ow2, the baseline, ComputeF12 (:55-71), the epipole
+ *                                 (src/ORBmatcher.cc:772-773) and the skip rule (:410-422: stereo
+ *                                 baseline < camera2.baseline; monocular baseline / ComputeSceneMedianDepth(2)
+ *                                 < 0.01f, src/KeyFrame.cc:522-552).  F12 / ep2 are what
+ *                                 orbm_search_for_triangulation_batch_device reads, in its layout.
+ *   orblm_triangulate             per match of that search's match12 (:437-560): the parallax test, linear
+ *                                 triangulation or uvZToWorld of either frame, the depth signs, both
+ *                                 reprojection gates, the scale gate; a status per keypoint of keyframe 1,
+ *                                 the created points compacted in ascending idx1 (the reference's creation
+ *                                 order) with what UpdateNormalAndDepth (src/MapPoint.cc:341-380) gives
+ *                                 them, and optionally the MapPoint flags of both keyframes set in place.
+ *   orblm_create_new_map_points   the neighbour loop: n_rounds x n_pairs plan entries; prepare once, then
+ *                                 per round the search followed by the triangulation with writable flags,
+ *                                 so that a point created against neighbour i hides its keypoints from the
+ *                                 search against neighbour i + 1, as keyframe1->GetMapPoint(idx1) does.
+ * All float arithmetic follows one fixed operation order (csrc/lm_newpoint.h), so F12, ep2, the baseline and
+ * the median are reproducible bit for bit.  Departure: a monocular pair whose keyframe 2 has no MapPoint is
+ * skipped (the reference indexes an empty vector).
+ * ---------------------------------------------------------------------------------------- */
+#define ORBLM_MAX_KP 8192          /* cap2 at most, where the median is taken (monocular) */
+enum {
+    ORBLM_CREATED = 0,             /* :562: the point is created */
+    ORBLM_NO_MATCH = 1,            /* match12[idx1] < 0 (or not a keypoint of keyframe 2) */
+    ORBLM_PAIR_SKIPPED = 2,        /* :410-422: a match of a skipped pair */
+    ORBLM_LOW_PARALLAX = 3,        /* :502 */
+    ORBLM_W_ZERO = 4,              /* :485: v(3) == 0 */
+    ORBLM_BEHIND1 = 5,             /* :507: Xc1.z <= 0 */
+    ORBLM_BEHIND2 = 6,             /* :507: Xc2.z <= 0 */
+    ORBLM_REPROJ1 = 7,             /* :514-525 */
+    ORBLM_REPROJ2 = 8,             /* :531-542 */
+    ORBLM_DIST_ZERO = 9,           /* :551 */
+    ORBLM_SCALE = 10               /* :559 */
+};
+enum { ORBLM_BRANCH_NONE = 0, ORBLM_BRANCH_TRIANGULATED = 1, ORBLM_BRANCH_STEREO1 = 2, ORBLM_BRANCH_STEREO2 = 3 };
+
+typedef struct orblm_batch {
+    int32_t n_pairs;                 /* pairs of one call; pairs per round for orblm_create_new_map_points */
+    int32_t cap1, cap2;              /* slots per keyframe of set 1 / set 2 (sets may be the same arrays) */
+    int32_t n_frames1, n_frames2;    /* keyframes in set 1 / set 2 */
+    const orbx_keypoint* kps1; const int32_t* counts1;   /* keypointsUn slots, as orbm_tri_batch */
+    const float* uright1; const float* depth1;            /* per slot; NULL: every keypoint monocular */
+    const orbx_keypoint* kps2; const int32_t* counts2;
+    const float* uright2; const float* depth2;
+    const uint8_t* has_mappoint2;    /* per slot of set 2: GetMapPoint(idx) != nullptr; monocular only */
+    const float* mp_xw2;             /* per slot of set 2 x 3: that MapPoint's GetWorldPos(); monocular only */
+    const float* pose1; const float* pose2;       /* per keyframe 12: Tcw as 3 x 4 row-major */
+    const float* camera1; const float* camera2;   /* per keyframe 6: fx, fy, cx, cy, bf, baseline */
+    const int32_t* frame1; const int32_t* frame2; /* per pair: keyframe of set 1 / set 2; negative: no pair */
+    int32_t n_levels;                /* <= ORBM_TRI_MAX_LEVELS */
+    const float* scale_factors1; const float* sigma2_1;   /* host, n_levels: keyframe 1's pyramid */
+    const float* scale_factors2; const float* sigma2_2;   /* host, n_levels: keyframe 2's pyramid */
+    float scale_factor;              /* keyframe1->pyramid.scaleFactor (ratioFactor = 1.5f x this) */
+    int32_t monocular;               /* which skip rule (:410) */
+} orblm_batch;
+
+/* What prepare writes and the other steps read, per pair (all required). */
+typedef struct orblm_pairs {
+    float* F12;            /* x 9 */
+    float* ep2;            /* x 2 */
+    float* baseline;
+    float* median;         /* medianDepthKF2 (0 where it is not taken) */
+    int32_t* skip;         /* 0 go on, 1 skipped by the rule, 2 no pair */
+    int32_t* frame1;       /* the pair's keyframes, 0 for "no pair": always valid indices for the search */
+    int32_t* frame2;
+    float* consts;         /* x 64: both keyframes' Tcw, Rwc, Ow and camera */
+} orblm_pairs;
+
+/* Per pair p and keypoint idx1 of keyframe 1, at p*cap1 + idx1 (written for idx1 < counts1). */
+typedef struct orblm_points {
+    int32_t* status;       /* ORBLM_* */
+    int32_t* branch;       /* ORBLM_BRANCH_* */
+    float* xw;             /* x 3: Xw where a branch was taken */
+    float* normal;         /* x 3, of a created point */
+    float* min_distance; float* max_distance;
+    int32_t* new_idx1;     /* k < n_created[p]: the created points in ascending idx1; -1 after them */
+    int32_t* new_idx2;
+    int32_t* n_created;    /* per pair */
+    uint8_t* has_mappoint1;/* per slot of set 1 / set 2: a created point sets its two flags; NULL: nothing */
+    uint8_t* has_mappoint2;/* is written (orblm_create_new_map_points needs both) */
+} orblm_points;
+
+/* Device forms: every array in HBM but the pyramid tables; enqueue only on `stream`.  A pair whose frame
+ * index is negative or not below n_frames1 / n_frames2 is "no pair": n_created = 0, nothing else written. */
+int orblm_prepare_pairs_device(const orblm_batch* b, const orblm_pairs* pairs, void* stream);
+/* d_match12[p*cap1 + idx1] as orbm_search_for_triangulation_batch_device leaves it. */
+int orblm_triangulate_device(const orblm_batch* b, const orblm_pairs* pairs, const int32_t* d_match12,
+                             const orblm_points* out, void* stream);
+/* The neighbour loop.  Plan entry (r, j) = (b->frame1[r*n_pairs + j], b->frame2[...]); every per-pair array of
+ * `pairs`, `out`, d_match12 and d_nmatches holds n_rounds*n_pairs pairs.  `search` gives what the search needs
+ * beyond `b` (desc1, desc2, the FeatureVectors, only_stereo, keyframe 2's tables); its slot arrays must be b's,
+ * its pair arrays and flags are replaced per round.  Precondition, not checked here (the plan is device
+ * memory): within one round all frame1 are distinct, all frame2 are distinct and, where the two sets are the
+ * same arrays, no keyframe is both; otherwise two pairs write one keyframe's flags.  Only enqueues: no
+ * synchronisation, no copy.  A caller that wants CheckNewKeyFrames() between neighbours (:401) enqueues round
+ * by round with the search and orblm_triangulate_device instead. */
+int orblm_create_new_map_points_device(const orblm_batch* b, const orbm_tri_batch* search, int32_t n_rounds,
+                                       const orblm_pairs* pairs, const orblm_points* out, int32_t* d_match12,
+                                       int32_t* d_nmatches, void* stream);
+/* Host forms: every pointer is host memory, synchronous; shapes, counts, octaves and the plan's precondition are
+ * validated before anything is copied.  out->has_mappoint1 / 2 are read and updated.
+ * orblm_create_new_map_points takes a search without FeatureVectors (one node holding every keypoint). */
+int orblm_prepare_pairs(const orblm_batch* b, const orblm_pairs* pairs, int device);
+int orblm_triangulate(const orblm_batch* b, const orblm_pairs* pairs, const int32_t* match12, const orblm_points* out,
+                      int device);
+int orblm_create_new_map_points(const orblm_batch* b, const orbm_tri_batch* search, int32_t n_rounds,
+                                const orblm_pairs* pairs, const orblm_points* out, int32_t* match12, int32_t* nmatches,
+                                int device);
 
 const char* orb_last_error(void);
 int orb_device_count(void);

@@ -592,6 +592,57 @@ private:
     orb_initializer_batch b_;
 };
 
+// LocalMapping::CreateNewMapPoints (src/LocalMapping.cc:380-578) on HBM-resident extractor slots.  The constructor takes
+// the keyframes (orblm_batch without a plan) and what the search needs beyond them (descriptors, FeatureVectors,
+// onlyStereo); Run takes the plan of n_rounds x n_pairs (keyframe 1, keyframe 2) entries, negative = none, as host
+// arrays (checked: within a round no keyframe twice, and none as both where the sets share their flags) and as
+// device arrays, and enqueues prepare and then per round the search and the triangulation.  The host allocates the
+// MapPoints from out.new_idx1 / new_idx2 / n_created afterwards.
+class CreateNewMapPoints {
+public:
+    CreateNewMapPoints(const orblm_batch& keyframes, const orbm_tri_batch& search) : b_(keyframes), s_(search) {}
+    void Run(int32_t n_rounds, int32_t n_pairs, const int32_t* h_frame1, const int32_t* h_frame2, const int32_t* d_frame1,
+             const int32_t* d_frame2, const orblm_pairs& pairs, const orblm_points& out, int32_t* d_match12,
+             int32_t* d_nmatches, void* stream = nullptr) {
+        CheckPlan(n_rounds, n_pairs, h_frame1, h_frame2, out.has_mappoint1 == out.has_mappoint2);
+        b_.n_pairs = n_pairs; b_.frame1 = d_frame1; b_.frame2 = d_frame2;
+        check(orblm_create_new_map_points_device(&b_, &s_, n_rounds, &pairs, &out, d_match12, d_nmatches, stream),
+              "orblm_create_new_map_points_device");
+    }
+    // One round by hand, for a caller that polls CheckNewKeyFrames() between neighbours (:401): PreparePairs once, then
+    // per round the search (SearchForTriangulationBatch on pairs.F12 / ep2 / frame1 / frame2) and Triangulate.
+    void PreparePairs(int32_t n_pairs, const int32_t* d_frame1, const int32_t* d_frame2, const orblm_pairs& pairs,
+                      void* stream = nullptr) {
+        b_.n_pairs = n_pairs; b_.frame1 = d_frame1; b_.frame2 = d_frame2;
+        check(orblm_prepare_pairs_device(&b_, &pairs, stream), "orblm_prepare_pairs_device");
+    }
+    void Triangulate(const orblm_pairs& pairs, const int32_t* d_match12, const orblm_points& out, void* stream = nullptr) {
+        check(orblm_triangulate_device(&b_, &pairs, d_match12, &out, stream), "orblm_triangulate_device");
+    }
+    static void CheckPlan(int32_t n_rounds, int32_t n_pairs, const int32_t* frame1, const int32_t* frame2, bool same_set) {
+        if (n_rounds < 0 || n_pairs < 0 || ((n_rounds && n_pairs) && (!frame1 || !frame2)))
+            throw std::invalid_argument("CreateNewMapPoints: bad plan");
+        for (int32_t r = 0; r < n_rounds; r++)
+            for (int32_t i = 0; i < n_pairs; i++) {
+                const int32_t a = frame1[r * n_pairs + i], c = frame2[r * n_pairs + i];
+                if ((a < 0) != (c < 0)) throw std::invalid_argument("CreateNewMapPoints: an entry with one keyframe only");
+                if (a < 0) continue;
+                for (int32_t j = 0; j < n_pairs; j++) {
+                    const int32_t a2 = frame1[r * n_pairs + j], c2 = frame2[r * n_pairs + j];
+                    if (a2 < 0) continue;
+                    if (j > i && (a2 == a || c2 == c)) throw std::invalid_argument("CreateNewMapPoints: a round names a keyframe twice");
+                    if (same_set && a == c2)
+                        throw std::invalid_argument("CreateNewMapPoints: a round names a keyframe as keyframe 1 and as keyframe 2");
+                }
+            }
+    }
+    const orblm_batch& batch() const { return b_; }
+
+private:
+    orblm_batch b_;
+    orbm_tri_batch s_;
+};
+
 // void MapPoint::ComputeDistinctiveDescriptors() (src/MapPoint.cc:257-320), batched over map points on HBM
 // arrays: point p holds the rows [begin[p], begin[p + 1]) of d_desc.  Enqueue only; best[p] = the winning
 // point-relative row (-1: empty), d_out_desc[p] = that row (an empty point's row is not written, so

@@ -11,6 +11,8 @@ Host mirrors of the reference's interfaces (tiantianxuabc/ORB_SLAM2_Refactored):
                                      (F, D, 4); make_draws is the Sim3 solver's (F, D, 3)
   InitializerInitialize           <- include/Initializer.h (src/Initializer.cc); its draw table is
                                      make_initializer_draws (F, T, 8)
+  PreparePairs / TriangulateMatches / CreateNewMapPoints <- LocalMapping::CreateNewMapPoints
+                                     (src/LocalMapping.cc:380-578), mapping.py
 All compute runs in liborbslam2_amd.so (HIP kernels behind include/orbslam2_amd.h).
 """
 from .extractor import ORBextractor, KP_DTYPE
@@ -21,9 +23,12 @@ from . import optimizer
 from .sim3solver import Sim3SolverIterate, sim3solver_iterate_device, make_draws
 from .pnpsolver import PnPsolverIterate, pnpsolver_iterate_device, make_draws as make_pnp_draws
 from .initializer import InitializerInitialize, initializer_initialize_device, make_draws as make_initializer_draws
+from .mapping import (PreparePairs, TriangulateMatches, CreateNewMapPoints, prepare_pairs_device,
+                      triangulate_matches_device, create_new_map_points_device)
 from .synth import synth_image, shifted_pair, stereo_pair, make_pose_batch
 
-__all__ = ["InitializerInitialize", "initializer_initialize_device", "make_initializer_draws", "PnPsolverIterate", "pnpsolver_iterate_device", "make_pnp_draws", "Sim3SolverIterate", "sim3solver_iterate_device", "make_draws", "ORBextractor", "ORBmatcher", "ComputeStereoMatches", "Fuse", "fuse_device", "SearchByProjectionSim3",
+__all__ = ["PreparePairs", "TriangulateMatches", "CreateNewMapPoints", "prepare_pairs_device", "triangulate_matches_device",
+           "create_new_map_points_device", "InitializerInitialize", "initializer_initialize_device", "make_initializer_draws", "PnPsolverIterate", "pnpsolver_iterate_device", "make_pnp_draws", "Sim3SolverIterate", "sim3solver_iterate_device", "make_draws", "ORBextractor", "ORBmatcher", "ComputeStereoMatches", "Fuse", "fuse_device", "SearchByProjectionSim3",
            "search_by_projection_sim3_device", "SearchBySim3", "search_by_sim3_device", "ComputeDistinctiveDescriptors",
            "compute_distinctive_descriptors_device", "optimizer", "KP_DTYPE", "synth_image", "shifted_pair", "stereo_pair",
            "make_pose_batch"]

@@ -215,6 +215,32 @@ class InitializerResult(C.Structure):
                 ("inlier_f", C.c_void_p), ("hyp_score", C.c_void_p), ("n_good", C.c_void_p), ("parallax", C.c_void_p)]
 
 
+class OrblmBatch(C.Structure):
+    """orblm_batch (include/orbslam2_amd.h)."""
+    _fields_ = [("n_pairs", C.c_int32), ("cap1", C.c_int32), ("cap2", C.c_int32), ("n_frames1", C.c_int32),
+                ("n_frames2", C.c_int32), ("kps1", C.c_void_p), ("counts1", C.c_void_p), ("uright1", C.c_void_p),
+                ("depth1", C.c_void_p), ("kps2", C.c_void_p), ("counts2", C.c_void_p), ("uright2", C.c_void_p),
+                ("depth2", C.c_void_p), ("has_mappoint2", C.c_void_p), ("mp_xw2", C.c_void_p), ("pose1", C.c_void_p),
+                ("pose2", C.c_void_p), ("camera1", C.c_void_p), ("camera2", C.c_void_p), ("frame1", C.c_void_p),
+                ("frame2", C.c_void_p), ("n_levels", C.c_int32), ("scale_factors1", C.c_void_p), ("sigma2_1", C.c_void_p),
+                ("scale_factors2", C.c_void_p), ("sigma2_2", C.c_void_p), ("scale_factor", C.c_float),
+                ("monocular", C.c_int32)]
+
+
+class OrblmPairs(C.Structure):
+    """orblm_pairs (include/orbslam2_amd.h)."""
+    _fields_ = [("F12", C.c_void_p), ("ep2", C.c_void_p), ("baseline", C.c_void_p), ("median", C.c_void_p),
+                ("skip", C.c_void_p), ("frame1", C.c_void_p), ("frame2", C.c_void_p), ("consts", C.c_void_p)]
+
+
+class OrblmPoints(C.Structure):
+    """orblm_points (include/orbslam2_amd.h)."""
+    _fields_ = [("status", C.c_void_p), ("branch", C.c_void_p), ("xw", C.c_void_p), ("normal", C.c_void_p),
+                ("min_distance", C.c_void_p), ("max_distance", C.c_void_p), ("new_idx1", C.c_void_p),
+                ("new_idx2", C.c_void_p), ("n_created", C.c_void_p), ("has_mappoint1", C.c_void_p),
+                ("has_mappoint2", C.c_void_p)]
+
+
 # cv::KeyPoint layout (28 bytes)
 KP_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("size", "<f4"), ("angle", "<f4"),
                      ("response", "<f4"), ("octave", "<i4"), ("class_id", "<i4")])
@@ -290,6 +316,14 @@ SIGNATURES = {
     "orb_pnpsolver_iterate_device": (C.c_int, [C.POINTER(PnPSolverBatch), C.POINTER(PnPSolverResult), VP]),
     "orb_initializer_initialize": (C.c_int, [C.POINTER(InitializerBatch), C.POINTER(InitializerResult), C.c_int]),
     "orb_initializer_initialize_device": (C.c_int, [C.POINTER(InitializerBatch), C.POINTER(InitializerResult), VP]),
+    "orblm_prepare_pairs": (C.c_int, [C.POINTER(OrblmBatch), C.POINTER(OrblmPairs), C.c_int]),
+    "orblm_prepare_pairs_device": (C.c_int, [C.POINTER(OrblmBatch), C.POINTER(OrblmPairs), VP]),
+    "orblm_triangulate": (C.c_int, [C.POINTER(OrblmBatch), C.POINTER(OrblmPairs), VP, C.POINTER(OrblmPoints), C.c_int]),
+    "orblm_triangulate_device": (C.c_int, [C.POINTER(OrblmBatch), C.POINTER(OrblmPairs), VP, C.POINTER(OrblmPoints), VP]),
+    "orblm_create_new_map_points": (C.c_int, [C.POINTER(OrblmBatch), C.POINTER(TriBatch), C.c_int32, C.POINTER(OrblmPairs),
+                                              C.POINTER(OrblmPoints), VP, VP, C.c_int]),
+    "orblm_create_new_map_points_device": (C.c_int, [C.POINTER(OrblmBatch), C.POINTER(TriBatch), C.c_int32,
+                                                     C.POINTER(OrblmPairs), C.POINTER(OrblmPoints), VP, VP, VP]),
     "orbx_pack_descriptors": (C.c_int,[VP, C.c_int, VP, VP, C.c_int, VP, C.c_int, VP]),
     "orbx_profile_enable": (C.c_int, [VP, C.c_int]),
     "orbx_profile_read": (C.c_int, [VP, VP, VP]),

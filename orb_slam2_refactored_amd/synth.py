@@ -1235,3 +1235,86 @@ def make_initializer_batch(seed: int = 0, n_corr=(150,), scene=("general",), out
                 camera=np.tile(np.array([fx, fy, cx, cy], np.float32), (F, 1)), draws=make_draws(F, max_iterations, seed),
                 rand_max=2147483647, sigma=1.0, max_iterations=int(max_iterations), min_parallax=1.0, min_triangulated=50,
                 rh_threshold=0.40, gt_r21t21=np.array(gts, np.float32).reshape(F, 12))
+
+
+def make_new_points_batch(seed: int = 0, n_kf1: int = 2, n_rounds: int = 3, cap: int = 130, counts=None, mode: str = "mixed",
+                          monocular=None, noise: float = 0.3, outlier_frac: float = 0.1, mp_frac: float = 0.15,
+                          short_frac: float = 0.2, baseline=(0.4, 1.2), along=(1.0, 0.4, 0.3)):
+    """CreateNewMapPoints inputs (orblm_batch, host arrays) shaped like LocalMapping's neighbour loop: n_kf1 current
+    keyframes with n_rounds neighbours each, all in one slot set of F = n_kf1 (1 + n_rounds) keyframes x cap slots
+    (keyframe k < n_kf1 is a current one, its neighbour of round r is n_kf1 + r n_kf1 + k).  Every keyframe sees the
+    same world points (depths 4 to 14) from its own pose with its own intrinsics (K1 != K2), `noise` px of Gaussian
+    noise, in its own slot order; a fraction outlier_frac of its keypoints lie 4 to 12 px off; descriptors are a world
+    point's 256 bits with a few flipped per view, so SearchForTriangulation finds the correspondences by itself.
+    mode: "mono" (uright = -1), "stereo" or "mixed" (half the keypoints carry uright / depth); monocular (the skip
+    rule) defaults to mode == "mono".  A fraction short_frac of the neighbours sits closer than either skip rule
+    allows, the others `baseline` away in a direction drawn with the per-axis weights `along`.  mp_frac of the slots already hold a MapPoint (has_mappoint, mp_xw).  counts: keypoints per keyframe
+    (default: cap).  Returns the arrays of mapping.py's batch (sets 1 and 2 are the same arrays), desc, has_mappoint
+    and the plan frame1 / frame2 [n_rounds, n_kf1]."""
+    from ._lib import KP_DTYPE
+    rng = np.random.default_rng(seed)
+    F = n_kf1 * (1 + n_rounds)
+    counts = np.full(F, cap, np.int32) if counts is None else np.asarray(counts, np.int32)
+    assert len(counts) == F and counts.max(initial=0) <= cap
+    mono = (mode == "mono") if monocular is None else bool(monocular)
+    b = 0.1
+    X = np.stack([rng.uniform(-4, 4, cap), rng.uniform(-3, 3, cap), rng.uniform(4, 14, cap)], 1)
+    base = rng.integers(0, 256, (cap, 32), dtype=np.uint8)
+    scale = np.cumprod(np.concatenate([[np.float32(1)], np.full(7, np.float32(1.2), np.float32)])).astype(np.float32)
+    kps = np.zeros((F, cap), KP_DTYPE)
+    desc = rng.integers(0, 256, (F, cap, 32), dtype=np.uint8)
+    ur = np.full((F, cap), -1, np.float32)
+    depth = np.full((F, cap), -1, np.float32)
+    mp = np.zeros((F, cap), np.uint8)
+    xw = np.zeros((F, cap, 3), np.float32)
+    pose = np.zeros((F, 12), np.float32)
+    cam = np.zeros((F, 6), np.float32)
+    for f in range(F):
+        w = rng.normal(0, 1, 3)
+        w *= np.deg2rad(rng.uniform(0.5, 4)) / np.linalg.norm(w)
+        th = np.linalg.norm(w)
+        kx = np.array([[0, -w[2], w[1]], [w[2], 0, -w[0]], [-w[1], w[0], 0]]) / th
+        R = np.eye(3) + np.sin(th) * kx + (1 - np.cos(th)) * (kx @ kx)
+        d = rng.normal(0, 1, 3) * np.asarray(along, np.float64)
+        d /= np.linalg.norm(d)
+        if f < n_kf1:
+            t = d * 0.05
+        else:
+            t = d * (rng.uniform(0.02, 0.06) if rng.random() < short_frac else rng.uniform(*baseline))
+        pose[f] = np.concatenate([R.astype(np.float32), t.astype(np.float32)[:, None]], 1).reshape(12)
+        fx, fy = 500.0 + 7 * f, 505.0 - 3 * f
+        cx, cy = 320.0 + 2 * f, 240.0 - f
+        cam[f] = [fx, fy, cx, cy, b * fx, b]
+        n = int(counts[f])
+        order = rng.permutation(cap)[:n]
+        Xc = X[order] @ R.T + t
+        u = fx * Xc[:, 0] / Xc[:, 2] + cx + rng.normal(0, noise, n)
+        v = fy * Xc[:, 1] / Xc[:, 2] + cy + rng.normal(0, noise, n)
+        out = rng.random(n) < outlier_frac
+        ang, mag = rng.uniform(0, 2 * np.pi, n), rng.uniform(4, 12, n)
+        u = np.where(out, u + mag * np.cos(ang), u)
+        v = np.where(out, v + mag * np.sin(ang), v)
+        kps["x"][f, :n] = u
+        kps["y"][f, :n] = v
+        kps["size"][f, :n] = 31
+        kps["octave"][f, :n] = rng.integers(0, 3, n)
+        flips = np.zeros((n, 32), np.uint8)
+        for _ in range(6):
+            flips[np.arange(n), rng.integers(0, 32, n)] ^= (1 << rng.integers(0, 8, n)).astype(np.uint8)
+        desc[f, :n] = base[order] ^ flips
+        if mode != "mono":
+            st = np.ones(n, bool) if mode == "stereo" else rng.random(n) < 0.5
+            z = Xc[:, 2] + rng.normal(0, 0.02, n)
+            depth[f, :n] = np.where(st, z, -1)
+            ur[f, :n] = np.where(st, u - b * fx / z, -1)
+        has = rng.random(n) < mp_frac
+        mp[f, :n] = has
+        xw[f, :n] = np.where(has[:, None], X[order], 0)
+    k = np.arange(n_kf1, dtype=np.int32)
+    frame1 = np.tile(k, (n_rounds, 1))
+    frame2 = np.stack([n_kf1 + r * n_kf1 + k for r in range(n_rounds)]).astype(np.int32).reshape(n_rounds, n_kf1)
+    return dict(kps1=kps, kps2=kps, counts1=counts, counts2=counts, uright1=None if mode == "mono" else ur,
+                depth1=None if mode == "mono" else depth, uright2=None if mode == "mono" else ur,
+                depth2=None if mode == "mono" else depth, has_mappoint2=mp.copy(), mp_xw2=xw, pose1=pose, pose2=pose,
+                camera1=cam, camera2=cam, frame1=frame1, frame2=frame2, scale_factors2=scale, sigma2_2=(scale * scale).astype(np.float32),
+                scale_factor=1.2, monocular=mono, desc=desc, has_mappoint=mp)
