@@ -1202,6 +1202,94 @@ int orblm_create_new_map_points(const orblm_batch* b, const orbm_tri_batch* sear
                                 const orblm_pairs* pairs, const orblm_points* out, int32_t* match12, int32_t* nmatches,
                                 int device);
 
+/* ------------------------------------------------------------------------------------------
+ * KeyFrameDatabase (include/KeyFrameDatabase.h, src/KeyFrameDatabase.cc:34-265) resident in HBM: add / erase /
+ * clear, DetectLoopCandidates (:68-171) and DetectRelocalizationCandidates (:173-265) batched over query frames,
+ * and the minScore loop of LoopDetector::Detect (src/LoopClosing.cc:170-178).  voc_->score is L1Scoring::score
+ * (Thirdparty/DBoW2/DBoW2/ScoringObject.cpp:23-68), the only scoring supported.
+ *
+ * A keyframe is a slot k in [0, max_keyframes): the host's index for its KeyFrame*.  A slot holds a live flag,
+ * its BowVector (word ids ascending, fp64 weights, at most word_cap entries, as orbv_transform* emits them) and
+ * one persistent float, reloc_score (KeyFrame::relocScore; the reference never initialises it, add sets 0).
+ * There is no inverted file: words[q][k], the number of word ids query q shares with live slot k (loopWords /
+ * relocWords after the walk of :78-93 / :181-193), is found by looking every word of the slot up in the query.
+ *
+ * Query q, with S = the live slots with words > 0 (loop form: and not in the query's connected set):
+ *   maxw = max words over S, minw = (int)(0.8f * (float)maxw); the slots of S with words > minw are scored:
+ *   score[q][k] = (float)voc.score(query, slot).  Relocalisation also stores it in reloc_score[k].
+ *   Every scored k (loop form: with score >= min_score[q]) opens a group: acc = best = score, bestk = k; its
+ *   covis[k][0..9] in order, -1 and slots outside S skipped (loop form: and slots this query did not score),
+ *   add their score to acc (float) and take bestk where it is > best.  Relocalisation adds reloc_score[nb], which
+ *   for a slot of S this query did not score is what the latest earlier query that scored it left (:239-247).
+ *   bestAcc = max over the groups' acc, starting from 0 (loop form: min_score[q]); the candidates are the set of
+ *   bestk of the groups with acc > 0.75f * bestAcc, ascending slot ids (the reference's std::set<KeyFrame*>).
+ * A batch of Q queries gives the result of the Q calls in order q = 0 .. Q-1: loop queries are independent,
+ * relocalisation queries are coupled through reloc_score (a last-writer scan over q per slot).
+ *
+ * Outputs: cand[q*max_keyframes ..] ascending (the rest -1) and n_cand[q]; optional (NULL to skip), each
+ * [Q][max_keyframes]: words, scored, score (0 where not scored), acc (0 where no group), bestk (-1 where none).
+ * A database's calls share one workspace: enqueue them on one stream at a time.
+ * ---------------------------------------------------------------------------------------- */
+typedef struct orbdb_database orbdb_database;
+#define ORBDB_COVIS 10   /* GetBestCovisibilityKeyFrames(10) */
+
+typedef struct orbdb_query_batch {
+    int32_t n_queries;
+    int32_t cap;                 /* the query BowVectors in orbv_transform_batch_device's layout: frame f at f*cap */
+    int32_t n_frames;            /* frames in the three arrays */
+    const uint32_t* bow_word; const double* bow_weight; const int32_t* n_words;
+    const int32_t* frame;        /* query q is frame frame[q] (NULL: q); outside [0, n_frames) = an empty query */
+    const int32_t* covis;        /* [max_keyframes][ORBDB_COVIS] slots, -1 padded, GetBestCovisibilityKeyFrames(10) order */
+    /* loop form only: */
+    const int32_t* conn_off;     /* [n_queries + 1] CSR of GetConnectedKeyFrames() as slots (the query's own slot too, */
+    const int32_t* conn_idx;     /* if it is live); entries outside [0, max_keyframes) are ignored */
+    const float* min_score;      /* [n_queries], e.g. orbdb_min_score_device's output */
+} orbdb_query_batch;
+
+typedef struct orbdb_result {
+    int32_t* cand; int32_t* n_cand;
+    int32_t* words; uint8_t* scored; float* score; float* acc; int32_t* bestk;   /* optional */
+} orbdb_result;
+
+/* KeyFrameDatabase(const ORBVocabulary&) (:34-37).  ORB_EINVAL unless the vocabulary's scoring is L1_NORM (0),
+ * 1 <= max_keyframes <= 1048576 and 1 <= word_cap <= ORBV_MAX_FEATURES.  All slots start erased. */
+int orbdb_create(const orbv_vocabulary* voc, int max_keyframes, int word_cap, int device, orbdb_database** out);
+int orbdb_destroy(orbdb_database* db);
+int orbdb_info(const orbdb_database* db, int* max_keyframes, int* word_cap);
+/* clear() (:62-66): every slot erased.  Enqueue only on `stream`. */
+int orbdb_clear(orbdb_database* db, void* stream);
+/* add(KeyFrame*) (:39-45) for n keyframes: slot d_slot[i] takes the BowVector of frame d_frame[i] (NULL: i) of an
+ * orbv_transform_batch_device output (stride cap, n_frames frames), becomes live and gets reloc_score 0.  The
+ * slots of one call are distinct.  An entry whose slot, frame or word count (> word_cap) is out of range is left
+ * out (device memory cannot be validated here; orbdb_add refuses it).  Enqueue only on `stream`. */
+int orbdb_add_device(orbdb_database* db, int n, const int32_t* d_slot, const int32_t* d_frame,
+                     const uint32_t* d_bow_word, const double* d_bow_weight, const int32_t* d_n_words, int cap,
+                     int n_frames, void* stream);
+/* erase(KeyFrame*) (:47-60): a flag store per slot; out-of-range slots are ignored.  Enqueue only on `stream`. */
+int orbdb_erase_device(orbdb_database* db, int n, const int32_t* d_slot, void* stream);
+/* LoopDetector::Detect's minScore (LoopClosing.cc:170-178): d_min_score[q] = min(1.f, (float)score(query q, slot k))
+ * over the slots k of d_cov_idx[d_cov_off[q] .. d_cov_off[q+1]) (GetVectorCovisibleKeyFrames(); the host leaves out
+ * isBad() ones; erased or out-of-range slots are skipped).  b->covis and the loop fields are not read.  Enqueue
+ * only on `stream`. */
+int orbdb_min_score_device(orbdb_database* db, const orbdb_query_batch* b, const int32_t* d_cov_off,
+                           const int32_t* d_cov_idx, float* d_min_score, void* stream);
+/* DetectRelocalizationCandidates (:173-265) / DetectLoopCandidates (:68-171) as described above; every array in
+ * HBM; enqueue only on `stream`, nothing is read back. */
+int orbdb_detect_reloc_device(orbdb_database* db, const orbdb_query_batch* b, const orbdb_result* out, void* stream);
+int orbdb_detect_loop_device(orbdb_database* db, const orbdb_query_batch* b, const orbdb_result* out, void* stream);
+/* Host-memory forms, synchronous.  Slots, frames, word counts, the covisibility table and the CSR lists are
+ * validated before anything is copied: ORB_EINVAL for a slot outside [0, max_keyframes) or named twice, a frame
+ * outside [0, n_frames), n_words > word_cap (add) or > cap, Q < 0, a NULL required array. */
+int orbdb_add(orbdb_database* db, int n, const int32_t* slot, const int32_t* frame, const uint32_t* bow_word,
+              const double* bow_weight, const int32_t* n_words, int cap, int n_frames);
+int orbdb_erase(orbdb_database* db, int n, const int32_t* slot);
+int orbdb_min_score(orbdb_database* db, const orbdb_query_batch* b, const int32_t* cov_off, const int32_t* cov_idx,
+                    float* min_score);
+int orbdb_detect_reloc(orbdb_database* db, const orbdb_query_batch* b, const orbdb_result* out);
+int orbdb_detect_loop(orbdb_database* db, const orbdb_query_batch* b, const orbdb_result* out);
+/* The slots' state, synchronous: live[k] and reloc_score[k], max_keyframes entries each (either may be NULL). */
+int orbdb_read_slots(orbdb_database* db, uint8_t* live, float* reloc_score);
+
 const char* orb_last_error(void);
 int orb_device_count(void);
 

@@ -708,6 +708,47 @@ private:
     orbv_vocabulary* h_ = nullptr;
 };
 
+// KeyFrameDatabase (include/KeyFrameDatabase.h, src/KeyFrameDatabase.cc:34-265) on slots: the host keeps the
+// KeyFrame* <-> slot table, the covisibility table (GetBestCovisibilityKeyFrames(10) per slot, -1 padded), the
+// connected sets and the consistency groups of LoopDetector::Detect (src/LoopClosing.cc:190-241); the BowVectors,
+// the common-word counts, the scores and the candidate sets stay in HBM.  The device methods only enqueue; arrays
+// are device memory in orbv_transform_batch_device's layout.
+class KeyFrameDatabase {
+public:
+    KeyFrameDatabase(const orbv_vocabulary* voc, int max_keyframes, int word_cap, int device = 0) {
+        check(orbdb_create(voc, max_keyframes, word_cap, device, &h_), "orbdb_create");
+    }
+    ~KeyFrameDatabase() { orbdb_destroy(h_); }
+    KeyFrameDatabase(const KeyFrameDatabase&) = delete;
+    KeyFrameDatabase& operator=(const KeyFrameDatabase&) = delete;
+
+    // add(KeyFrame*) for n keyframes: slot d_slot[i] takes frame d_frame[i] (nullptr: i) of the transform output
+    void add(int n, const int32_t* d_slot, const int32_t* d_frame, const uint32_t* d_bow_word, const double* d_bow_weight,
+             const int32_t* d_n_words, int cap, int n_frames, void* stream = nullptr) {
+        check(orbdb_add_device(h_, n, d_slot, d_frame, d_bow_word, d_bow_weight, d_n_words, cap, n_frames, stream),
+              "orbdb_add_device");
+    }
+    void erase(int n, const int32_t* d_slot, void* stream = nullptr) {
+        check(orbdb_erase_device(h_, n, d_slot, stream), "orbdb_erase_device");
+    }
+    void clear(void* stream = nullptr) { check(orbdb_clear(h_, stream), "orbdb_clear"); }
+    // LoopDetector::Detect's minScore (LoopClosing.cc:170-178) into d_min_score, which DetectLoopCandidates reads
+    void MinScore(const orbdb_query_batch& b, const int32_t* d_cov_off, const int32_t* d_cov_idx, float* d_min_score,
+                  void* stream = nullptr) {
+        check(orbdb_min_score_device(h_, &b, d_cov_off, d_cov_idx, d_min_score, stream), "orbdb_min_score_device");
+    }
+    void DetectLoopCandidates(const orbdb_query_batch& b, const orbdb_result& out, void* stream = nullptr) {
+        check(orbdb_detect_loop_device(h_, &b, &out, stream), "orbdb_detect_loop_device");
+    }
+    void DetectRelocalizationCandidates(const orbdb_query_batch& b, const orbdb_result& out, void* stream = nullptr) {
+        check(orbdb_detect_reloc_device(h_, &b, &out, stream), "orbdb_detect_reloc_device");
+    }
+    orbdb_database* handle() const { return h_; }
+
+private:
+    orbdb_database* h_ = nullptr;
+};
+
 }  // namespace ORB_SLAM2_AMD
 
 #endif  // ORBSLAM2_AMD_HPP

@@ -13,6 +13,8 @@ Host mirrors of the reference's interfaces (tiantianxuabc/ORB_SLAM2_Refactored):
                                      make_initializer_draws (F, T, 8)
   PreparePairs / TriangulateMatches / CreateNewMapPoints <- LocalMapping::CreateNewMapPoints
                                      (src/LocalMapping.cc:380-578), mapping.py
+  KeyFrameDatabase                <- include/KeyFrameDatabase.h (src/KeyFrameDatabase.cc) and Detect's minScore
+                                     (src/LoopClosing.cc:170-178), keyframe_db.py
 All compute runs in liborbslam2_amd.so (HIP kernels behind include/orbslam2_amd.h).
 """
 from .extractor import ORBextractor, KP_DTYPE
@@ -25,9 +27,10 @@ from .pnpsolver import PnPsolverIterate, pnpsolver_iterate_device, make_draws as
 from .initializer import InitializerInitialize, initializer_initialize_device, make_draws as make_initializer_draws
 from .mapping import (PreparePairs, TriangulateMatches, CreateNewMapPoints, prepare_pairs_device,
                       triangulate_matches_device, create_new_map_points_device)
+from .keyframe_db import KeyFrameDatabase
 from .synth import synth_image, shifted_pair, stereo_pair, make_pose_batch
 
-__all__ = ["PreparePairs", "TriangulateMatches", "CreateNewMapPoints", "prepare_pairs_device", "triangulate_matches_device",
+__all__ = ["KeyFrameDatabase", "PreparePairs", "TriangulateMatches", "CreateNewMapPoints", "prepare_pairs_device", "triangulate_matches_device",
            "create_new_map_points_device", "InitializerInitialize", "initializer_initialize_device", "make_initializer_draws", "PnPsolverIterate", "pnpsolver_iterate_device", "make_pnp_draws", "Sim3SolverIterate", "sim3solver_iterate_device", "make_draws", "ORBextractor", "ORBmatcher", "ComputeStereoMatches", "Fuse", "fuse_device", "SearchByProjectionSim3",
            "search_by_projection_sim3_device", "SearchBySim3", "search_by_sim3_device", "ComputeDistinctiveDescriptors",
            "compute_distinctive_descriptors_device", "optimizer", "KP_DTYPE", "synth_image", "shifted_pair", "stereo_pair",

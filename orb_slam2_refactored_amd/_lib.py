@@ -241,6 +241,19 @@ class OrblmPoints(C.Structure):
                 ("has_mappoint2", C.c_void_p)]
 
 
+class OrbdbQueryBatch(C.Structure):
+    """orbdb_query_batch (include/orbslam2_amd.h)."""
+    _fields_ = [("n_queries", C.c_int32), ("cap", C.c_int32), ("n_frames", C.c_int32), ("bow_word", C.c_void_p),
+                ("bow_weight", C.c_void_p), ("n_words", C.c_void_p), ("frame", C.c_void_p), ("covis", C.c_void_p),
+                ("conn_off", C.c_void_p), ("conn_idx", C.c_void_p), ("min_score", C.c_void_p)]
+
+
+class OrbdbResult(C.Structure):
+    """orbdb_result (include/orbslam2_amd.h)."""
+    _fields_ = [("cand", C.c_void_p), ("n_cand", C.c_void_p), ("words", C.c_void_p), ("scored", C.c_void_p),
+                ("score", C.c_void_p), ("acc", C.c_void_p), ("bestk", C.c_void_p)]
+
+
 # cv::KeyPoint layout (28 bytes)
 KP_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("size", "<f4"), ("angle", "<f4"),
                      ("response", "<f4"), ("octave", "<i4"), ("class_id", "<i4")])
@@ -324,6 +337,21 @@ SIGNATURES = {
                                               C.POINTER(OrblmPoints), VP, VP, C.c_int]),
     "orblm_create_new_map_points_device": (C.c_int, [C.POINTER(OrblmBatch), C.POINTER(TriBatch), C.c_int32,
                                                      C.POINTER(OrblmPairs), C.POINTER(OrblmPoints), VP, VP, VP]),
+    "orbdb_create": (C.c_int, [VP, C.c_int, C.c_int, C.c_int, C.POINTER(VP)]),
+    "orbdb_destroy": (C.c_int, [VP]),
+    "orbdb_info": (C.c_int, [VP, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "orbdb_clear": (C.c_int, [VP, VP]),
+    "orbdb_add_device": (C.c_int, [VP, C.c_int, VP, VP, VP, VP, VP, C.c_int, C.c_int, VP]),
+    "orbdb_erase_device": (C.c_int, [VP, C.c_int, VP, VP]),
+    "orbdb_min_score_device": (C.c_int, [VP, C.POINTER(OrbdbQueryBatch), VP, VP, VP, VP]),
+    "orbdb_detect_reloc_device": (C.c_int, [VP, C.POINTER(OrbdbQueryBatch), C.POINTER(OrbdbResult), VP]),
+    "orbdb_detect_loop_device": (C.c_int, [VP, C.POINTER(OrbdbQueryBatch), C.POINTER(OrbdbResult), VP]),
+    "orbdb_add": (C.c_int, [VP, C.c_int, VP, VP, VP, VP, VP, C.c_int, C.c_int]),
+    "orbdb_erase": (C.c_int, [VP, C.c_int, VP]),
+    "orbdb_min_score": (C.c_int, [VP, C.POINTER(OrbdbQueryBatch), VP, VP, VP]),
+    "orbdb_detect_reloc": (C.c_int, [VP, C.POINTER(OrbdbQueryBatch), C.POINTER(OrbdbResult)]),
+    "orbdb_detect_loop": (C.c_int, [VP, C.POINTER(OrbdbQueryBatch), C.POINTER(OrbdbResult)]),
+    "orbdb_read_slots": (C.c_int, [VP, VP, VP]),
     "orbx_pack_descriptors": (C.c_int,[VP, C.c_int, VP, VP, C.c_int, VP, C.c_int, VP]),
     "orbx_profile_enable": (C.c_int, [VP, C.c_int]),
     "orbx_profile_read": (C.c_int, [VP, VP, VP]),

@@ -1318,3 +1318,93 @@ def make_new_points_batch(seed: int = 0, n_kf1: int = 2, n_rounds: int = 3, cap:
                 depth2=None if mode == "mono" else depth, has_mappoint2=mp.copy(), mp_xw2=xw, pose1=pose, pose2=pose,
                 camera1=cam, camera2=cam, frame1=frame1, frame2=frame2, scale_factors2=scale, sigma2_2=(scale * scale).astype(np.float32),
                 scale_factor=1.2, monocular=mono, desc=desc, has_mappoint=mp)
+
+
+def make_keyframe_db_case(seed: int = 0, max_keyframes: int = 70, n_add: int = 68, n_erased: int = 3, word_cap: int = 200,
+                          n_places: int = 5, n_queries: int = 5, counts=None, q_counts=None, vocab: int = 4000,
+                          share: float = 0.85, q_cap: int = None):
+    """A KeyFrameDatabase case (KeyFrameDatabase.cc:34-265): BowVectors built directly (word ids ascending, L1-normalised
+    fp64 weights), a covisibility table, connected sets, covisible lists and queries.
+
+    Keyframes are grouped into `n_places` places.  A place owns `word_cap` words; a keyframe of `counts[i]` words takes
+    about `share` of them from its place and the rest from a small common pool, so keyframes of one place share most of
+    their words, keyframes of different places a few, and the short ones of a place fall below 0.8 x the most shared.
+    Each place has two visits: a query of the place (a further keyframe of it) is connected to the first visit only, the
+    second is what a loop query should find.  Covisibility rows name keyframes of the same place first, then some of the
+    next place, an erased slot and an unused one here and there, -1 padded.  Consecutive queries alternate between two
+    neighbouring places, so a relocalisation query meets scores left by the one before.
+
+    Returns dict(max_keyframes, word_cap, slot (n_add,), bow_word / bow_weight (n_add, word_cap), n_words (n_add,), erased,
+    place (max_keyframes,; -1 unused), covis (max_keyframes, 10), n_queries, q_cap, q_bow_word / q_bow_weight (F, q_cap),
+    q_n_words (F,), q_frame (Q,), q_place (Q,), conn_off / conn_idx, cov_off / cov_idx)."""
+    rng = np.random.default_rng(seed)
+    K, W = max_keyframes, word_cap
+    q_cap = q_cap or W
+    pool = rng.choice(vocab, size=max(W // 2, 8), replace=False)                      # words every place may use
+    rest = np.setdiff1d(np.arange(vocab), pool)
+    place_words = [rng.choice(rest, size=W, replace=False) for _ in range(n_places)]
+    idf = rng.uniform(0.5, 8.0, vocab)
+
+    def bow(place, n):
+        n_own = min(int(round(share * n)), W)
+        if n == 1:
+            n_own = 1
+        own = rng.choice(place_words[place], size=n_own, replace=False)
+        other = rng.choice(pool, size=min(n - n_own, len(pool)), replace=False)
+        w = np.unique(np.concatenate([own, other])).astype(np.uint32)
+        v = idf[w] * rng.integers(1, 4, len(w))
+        return w, (v / v.sum() if len(w) else v)
+
+    if counts is None:
+        counts = rng.integers(int(0.3 * W), W + 1, n_add)
+        counts[rng.random(n_add) < 0.5] = rng.integers(int(0.85 * W), W + 1)
+    counts = np.resize(np.asarray(counts, np.int64), n_add)
+    slot = rng.permutation(K)[:n_add].astype(np.int32)
+    place_of_add = np.arange(n_add) % n_places
+    visit_of_add = (np.arange(n_add) // n_places) % 2
+    bw, bv, nw = np.zeros((n_add, W), np.uint32), np.zeros((n_add, W)), np.zeros(n_add, np.int32)
+    for i in range(n_add):
+        w, v = bow(int(place_of_add[i]), int(counts[i]))
+        nw[i] = len(w)
+        bw[i, :len(w)], bv[i, :len(w)] = w, v
+    erased = slot[rng.choice(n_add, size=n_erased, replace=False)] if n_erased else np.zeros(0, np.int32)
+    place = np.full(K, -1, np.int32)
+    visit = np.full(K, -1, np.int32)
+    place[slot], visit[slot] = place_of_add, visit_of_add
+    unused = np.setdiff1d(np.arange(K), slot)
+    covis = np.full((K, 10), -1, np.int32)
+    for k in slot:
+        same = rng.permutation(np.flatnonzero((place == place[k]) & (np.arange(K) != k)))
+        nxt = rng.permutation(np.flatnonzero(place == (place[k] + 1) % n_places))
+        row = list(same[:int(rng.integers(0, 7))]) + list(nxt[:int(rng.integers(0, 4))])
+        if len(unused) and rng.random() < 0.2:
+            row.append(int(rng.choice(unused)))
+        row = [int(x) for x in rng.permutation(row)][:10] if rng.random() < 0.5 else [int(x) for x in row][:10]
+        covis[k, :len(row)] = row
+    Q = n_queries
+    F = Q + 1
+    q_frame = rng.permutation(F)[:Q].astype(np.int32)
+    if q_counts is None:
+        q_counts = rng.integers(int(0.8 * W), min(W, q_cap) + 1, Q)
+    q_counts = np.resize(np.asarray(q_counts, np.int64), Q)
+    first = int(rng.integers(0, n_places))
+    q_place = np.array([(first + (q % 2)) % n_places for q in range(Q)], np.int32)
+    qw, qv, qn = np.zeros((F, q_cap), np.uint32), np.zeros((F, q_cap)), np.zeros(F, np.int32)
+    conn_off, conn_idx, cov_off, cov_idx = [0], [], [0], []
+    for q in range(Q):
+        w, v = bow(int(q_place[q]), int(q_counts[q]))
+        f = q_frame[q]
+        qn[f] = len(w)
+        qw[f, :len(w)], qv[f, :len(w)] = w, v
+        conn = [int(k) for k in rng.permutation(np.flatnonzero((place == q_place[q]) & (visit == 0)))]
+        if len(unused):
+            conn.append(int(unused[q % len(unused)]))
+        conn_idx += conn
+        conn_off.append(len(conn_idx))
+        cov = [k for k in conn if rng.random() < 0.7]
+        cov_idx += cov
+        cov_off.append(len(cov_idx))
+    return dict(max_keyframes=K, word_cap=W, slot=slot, bow_word=bw, bow_weight=bv, n_words=nw, erased=np.asarray(erased, np.int32),
+                place=place, covis=covis, n_queries=Q, q_cap=q_cap, q_bow_word=qw, q_bow_weight=qv, q_n_words=qn, q_frame=q_frame,
+                q_place=q_place, conn_off=np.asarray(conn_off, np.int32), conn_idx=np.asarray(conn_idx, np.int32),
+                cov_off=np.asarray(cov_off, np.int32), cov_idx=np.asarray(cov_idx, np.int32))
