@@ -1290,6 +1290,119 @@ int orbdb_detect_loop(orbdb_database* db, const orbdb_query_batch* b, const orbd
 /* The slots' state, synchronous: live[k] and reloc_score[k], max_keyframes entries each (either may be NULL). */
 int orbdb_read_slots(orbdb_database* db, uint8_t* live, float* reloc_score);
 
+/* ------------------------------------------------------------------------------------------
+ * Tracking's local map: LocalMap::Update (src/Tracking.cc:59-179: UpdateLocalKeyFrames, UpdateLocalPoints) and
+ * SearchLocalPoints up to the matcher call (:607-642, IsInFrustum :554-605), batched over frames.  The outputs are
+ * the arrays of an orbm_proj_batch, so orbm_search_by_projection_device is enqueued behind this call on the same
+ * stream with nothing copied back; orbba_pose_optimization_device follows it: TrackLocalMap (:651-683).
+ *
+ * The map is slot tables the caller owns.  Keyframe slot k in [0, n_keyframes), map-point slot m in
+ * [0, n_mappoints); -1 is a null pointer.  Per frame f, in this order:
+ *  1 votes (:72-88): every frame_mappoint[f][i], i < frame_n[f], that is >= 0 and not bad adds 1 to
+ *    votes[f][k] for each k of its observation list; a bad one is set to -1 in frame_mappoint.
+ *  2 first part (:90-116): with no vote at all the call leaves local_kf / n_local_kf as they came in and
+ *    reference_kf[f] = -1 (unchanged).  Otherwise the list is cleared and every voted, non-bad k appended and
+ *    marked; reference_kf[f] = the first with a strictly greater count (-1 when all voted ones are bad).
+ *  3 second part (:119-156): for each element of the first part, in order: stop when the list holds more than 80;
+ *    append the first non-bad unmarked entry of kf_covis[k]; the first non-bad unmarked child; the parent if it
+ *    is unmarked (bad or not), and then stop the whole walk (the break of :152 leaves the outer loop).
+ *  4 UpdateLocalPoints (:165-179): the map points of the listed keyframes in list order, then keypoint order
+ *    (kf_mappoint[k][0 .. kf_n[k])), each at its first occurrence, null and bad ones left out: local_mp[f][..],
+ *    n_local_mp[f].
+ *  5 :610-625: every non-null frame_mappoint[f][i] gets mp_visible += 1 and is not projected (lastFrameSeen).
+ *  6 :631-642: every other local point runs IsInFrustum with min_view_cos; a passing one gets mp_visible += 1;
+ *    n_to_match[f] counts them.
+ * Departure from the reference: it walks a std::map<KeyFrame*, int> (the votes) and a std::set<KeyFrame*> (the
+ * children) in pointer order, which no two runs share.  Here both are walked in ascending slot order.
+ *
+ * Outputs for local point j of frame f, at f*mp_cap + j: mp_valid (in frustum = trackInView && !isBad()), mp_proj
+ * (u, v, u - bf/z), mp_view_cos, mp_level (all 0 where mp_valid is 0), mp_desc and mp_has_obs (mp_nobs > 0) for
+ * every j < n_local_mp[f]; slots from n_local_mp[f] on hold mp_valid 0, local_mp -1 and zeros.  mp_begin[f] =
+ * f*mp_cap and kp_begin[f] = f*kp_cap (F + 1 entries each) make them an orbm_proj_batch over keypoint arrays of
+ * stride kp_cap without a pass across frames.  kp_claimed[f*kp_cap + i] = frame_mappoint >= 0 && mp_nobs > 0
+ * (after step 1), and 1 for the padding i >= frame_n[f], which the search therefore never matches (give the
+ * padding any finite kp_xy).
+ *
+ * status[f]: ORBTL_OK, or ORBTL_KF_OVERFLOW (steps 2-3 built more than kf_list_cap keyframes; local_kf keeps the
+ * first kf_list_cap, n_local_kf[f] = kf_list_cap), or ORBTL_MP_OVERFLOW (step 4 found more than mp_cap points).
+ * Such a frame gets n_to_match[f] = -1, n_local_mp[f] = 0, no local point and no mp_visible increment; nothing is
+ * written out of bounds and the other frames are unaffected.
+ * Frames of a batch are independent except that their mp_visible increments add up (integer atomics: a batch
+ * equals its frames run one at a time, in any order).  Two frames of one batch must not share a local_kf row.
+ *
+ * Workspace (per thread, grow-only, as the projection searches'): per (frame, map point) a uint32 first-occurrence
+ * key (list position * kf_cap + index, by atomicMin) and a seen byte, per (frame, keyframe) a mark byte and, when
+ * votes is NULL, the int32 votes: n_frames * (5 * n_mappoints + 5 * n_keyframes + 4 * kf_list_cap) bytes.
+ * ---------------------------------------------------------------------------------------- */
+#define ORBTL_OK 0
+#define ORBTL_KF_OVERFLOW 1
+#define ORBTL_MP_OVERFLOW 2
+#define ORBTL_MAX_KEYFRAMES 80   /* the walk of step 3 stops once the list holds more (:122) */
+
+typedef struct orbtl_map {
+    int32_t n_keyframes, n_mappoints, kf_cap;
+    const uint8_t* kf_bad;        /* [K] isBad() */
+    const int32_t* kf_covis;      /* [K][ORBDB_COVIS] GetBestCovisibilityKeyFrames(10) order, -1 padded (orbdb_query_batch.covis) */
+    const int32_t* kf_parent;     /* [K] GetParent(), -1 for none */
+    const int32_t* kf_child_off;  /* [K + 1] CSR of GetChildren(), each list ascending */
+    const int32_t* kf_child_idx;
+    const int32_t* kf_n;          /* [K] N */
+    const int32_t* kf_mappoint;   /* [K][kf_cap] GetMapPointMatches() */
+    const uint8_t* mp_bad;        /* [M] */
+    const float* mp_xw;           /* [M][3] GetWorldPos() */
+    const float* mp_normal;       /* [M][3] GetNormal() */
+    const float* mp_max_min;      /* [M][2] maxDistance_, minDistance_ (raw, as orbm_reloc_batch takes them) */
+    const uint8_t* mp_desc;       /* [M][32] GetDescriptor() */
+    const int32_t* mp_nobs;       /* [M] Observations() */
+    const int32_t* mp_obs_off;    /* [M + 1] CSR of GetObservations() keys as keyframe slots */
+    const int32_t* mp_obs_kf;
+    int32_t* mp_visible;          /* [M] read and updated: IncreaseVisible() */
+} orbtl_map;
+
+typedef struct orbtl_frames {
+    int32_t n_frames, kp_cap, kf_list_cap, mp_cap;
+    int32_t n_levels;             /* frame.pyramid.nlevels, 1 .. 32 */
+    float log_scale_factor;       /* frame.pyramid.logScaleFactor */
+    float min_view_cos;           /* 0.5f at the call site (:637) */
+    const int32_t* frame_n;       /* [F] N */
+    int32_t* frame_mappoint;      /* [F][kp_cap] read and updated (step 1) */
+    const float* pose;            /* [F][12] Rcw row-major, tcw */
+    const float* camera;          /* [F][5] fx, fy, cx, cy, bf */
+    const float* bounds;          /* [F][4] imageBounds minx, maxx, miny, maxy */
+    int32_t* local_kf;            /* [F][kf_list_cap] read and updated: LocalMap::keyframes of frame f's tracker */
+    int32_t* n_local_kf;          /* [F] */
+} orbtl_frames;
+
+typedef struct orbtl_result {
+    int32_t* reference_kf;        /* [F] */
+    int32_t* local_mp;            /* [F][mp_cap] */
+    int32_t* n_local_mp;          /* [F] */
+    int32_t* n_to_match;          /* [F] */
+    int32_t* status;              /* [F] */
+    int32_t* kp_begin;            /* [F + 1] f*kp_cap */
+    int32_t* mp_begin;            /* [F + 1] f*mp_cap */
+    uint8_t* kp_claimed;          /* [F][kp_cap] */
+    uint8_t* mp_valid;            /* [F][mp_cap] */
+    float* mp_proj;               /* [F][mp_cap][3] */
+    float* mp_view_cos;           /* [F][mp_cap] */
+    int32_t* mp_level;            /* [F][mp_cap] */
+    uint8_t* mp_desc;             /* [F][mp_cap][32] */
+    uint8_t* mp_has_obs;          /* [F][mp_cap] */
+    int32_t* votes;               /* optional (NULL to skip): [F][K] */
+} orbtl_result;
+
+/* Every array in HBM; enqueue only on `stream`: no synchronisation, no copy.  Slots read from device memory are
+ * not trusted: one outside its table is treated as null.  ORB_EINVAL for a NULL required array, negative sizes,
+ * kf_cap / kp_cap / kf_list_cap / mp_cap < 1, n_levels outside [1, 32], kf_list_cap * kf_cap >= 2^31 or a table of
+ * 2^31 entries or more. */
+int orbtl_track_local_map_device(const orbtl_map* map, const orbtl_frames* frames, const orbtl_result* out,
+                                 void* stream);
+/* Host memory, synchronous.  Before anything is copied: the checks above, every slot of every table in range
+ * (kf_covis, kf_parent, frame_mappoint, kf_mappoint in [-1, size); kf_child_idx, mp_obs_kf, local_kf in [0, size)),
+ * kf_n in [0, kf_cap], frame_n in [0, kp_cap], n_local_kf in [0, kf_list_cap], both CSR offset arrays starting at 0
+ * and not decreasing, log_scale_factor finite and > 0.  ORB_EINVAL otherwise. */
+int orbtl_track_local_map(const orbtl_map* map, const orbtl_frames* frames, const orbtl_result* out, int device);
+
 const char* orb_last_error(void);
 int orb_device_count(void);
 

@@ -749,6 +749,43 @@ private:
     orbdb_database* h_ = nullptr;
 };
 
+// Tracking's local map (src/Tracking.cc: LocalMap::Update :59-179 and SearchLocalPoints up to the matcher call :607-642):
+// the host keeps the KeyFrame* / MapPoint* <-> slot tables and owns the arrays of orbtl_map in HBM; TrackLocalMap enqueues
+// the votes, the keyframe list, the local points and the frustum pass for a batch of frames, then SearchByProjection on the
+// arrays it produced, on one stream with nothing copied back.  The keypoint arrays have stride frames.kp_cap.
+class LocalMap {
+public:
+    explicit LocalMap(const orbtl_map& map) : map_(map) {}
+
+    // LocalMap::Update + the frustum pass; out's arrays become search's map-point fields
+    void Update(const orbtl_frames& frames, const orbtl_result& out, void* stream = nullptr) const {
+        check(orbtl_track_local_map_device(&map_, &frames, &out, stream), "orbtl_track_local_map_device");
+    }
+    // TrackLocalMap up to PoseOptimization: Update, then ORBmatcher(nnratio).SearchByProjection(frame, mappoints, th).
+    // `kp` carries kp_xy, kp_octave, kp_uright, kp_desc, bounds, n_levels, scale_factors, th, nnratio; the rest is filled here.
+    void TrackLocalMap(const orbtl_frames& frames, const orbtl_result& out, orbm_proj_batch kp, int32_t* d_kp_match,
+                       int32_t* d_n_matches, void* stream = nullptr) const {
+        Update(frames, out, stream);
+        kp.n_frames = frames.n_frames;
+        kp.total_kp = frames.n_frames * frames.kp_cap;
+        kp.total_mp = frames.n_frames * frames.mp_cap;
+        kp.kp_begin = out.kp_begin;
+        kp.kp_claimed = out.kp_claimed;
+        kp.mp_begin = out.mp_begin;
+        kp.mp_valid = out.mp_valid;
+        kp.mp_proj = out.mp_proj;
+        kp.mp_view_cos = out.mp_view_cos;
+        kp.mp_level = out.mp_level;
+        kp.mp_desc = out.mp_desc;
+        kp.mp_has_obs = out.mp_has_obs;
+        check(orbm_search_by_projection_device(&kp, d_kp_match, d_n_matches, stream), "orbm_search_by_projection_device");
+    }
+    const orbtl_map& map() const { return map_; }
+
+private:
+    orbtl_map map_;
+};
+
 }  // namespace ORB_SLAM2_AMD
 
 #endif  // ORBSLAM2_AMD_HPP

@@ -15,6 +15,8 @@ Host mirrors of the reference's interfaces (tiantianxuabc/ORB_SLAM2_Refactored):
                                      (src/LocalMapping.cc:380-578), mapping.py
   KeyFrameDatabase                <- include/KeyFrameDatabase.h (src/KeyFrameDatabase.cc) and Detect's minScore
                                      (src/LoopClosing.cc:170-178), keyframe_db.py
+  LocalMap                        <- LocalMap::Update and SearchLocalPoints' frustum pass (src/Tracking.cc:59-179,
+                                     :554-642), local_map.py
 All compute runs in liborbslam2_amd.so (HIP kernels behind include/orbslam2_amd.h).
 """
 from .extractor import ORBextractor, KP_DTYPE
@@ -28,9 +30,10 @@ from .initializer import InitializerInitialize, initializer_initialize_device, m
 from .mapping import (PreparePairs, TriangulateMatches, CreateNewMapPoints, prepare_pairs_device,
                       triangulate_matches_device, create_new_map_points_device)
 from .keyframe_db import KeyFrameDatabase
+from .local_map import LocalMap
 from .synth import synth_image, shifted_pair, stereo_pair, make_pose_batch
 
-__all__ = ["KeyFrameDatabase", "PreparePairs", "TriangulateMatches", "CreateNewMapPoints", "prepare_pairs_device", "triangulate_matches_device",
+__all__ = ["KeyFrameDatabase", "LocalMap", "PreparePairs", "TriangulateMatches", "CreateNewMapPoints", "prepare_pairs_device", "triangulate_matches_device",
            "create_new_map_points_device", "InitializerInitialize", "initializer_initialize_device", "make_initializer_draws", "PnPsolverIterate", "pnpsolver_iterate_device", "make_pnp_draws", "Sim3SolverIterate", "sim3solver_iterate_device", "make_draws", "ORBextractor", "ORBmatcher", "ComputeStereoMatches", "Fuse", "fuse_device", "SearchByProjectionSim3",
            "search_by_projection_sim3_device", "SearchBySim3", "search_by_sim3_device", "ComputeDistinctiveDescriptors",
            "compute_distinctive_descriptors_device", "optimizer", "KP_DTYPE", "synth_image", "shifted_pair", "stereo_pair",

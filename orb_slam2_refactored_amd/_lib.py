@@ -263,6 +263,28 @@ I32 = C.c_int32
 SZ = C.c_size_t
 
 # name -> (restype, argtypes); every symbol declared in include/orbslam2_amd.h
+class OrbtlMap(C.Structure):
+    """orbtl_map (include/orbslam2_amd.h)."""
+    _fields_ = [("n_keyframes", C.c_int32), ("n_mappoints", C.c_int32), ("kf_cap", C.c_int32)] + [
+        (k, C.c_void_p) for k in ("kf_bad", "kf_covis", "kf_parent", "kf_child_off", "kf_child_idx", "kf_n", "kf_mappoint",
+                                  "mp_bad", "mp_xw", "mp_normal", "mp_max_min", "mp_desc", "mp_nobs", "mp_obs_off",
+                                  "mp_obs_kf", "mp_visible")]
+
+
+class OrbtlFrames(C.Structure):
+    """orbtl_frames (include/orbslam2_amd.h)."""
+    _fields_ = [("n_frames", C.c_int32), ("kp_cap", C.c_int32), ("kf_list_cap", C.c_int32), ("mp_cap", C.c_int32),
+                ("n_levels", C.c_int32), ("log_scale_factor", C.c_float), ("min_view_cos", C.c_float)] + [
+        (k, C.c_void_p) for k in ("frame_n", "frame_mappoint", "pose", "camera", "bounds", "local_kf", "n_local_kf")]
+
+
+class OrbtlResult(C.Structure):
+    """orbtl_result (include/orbslam2_amd.h)."""
+    _fields_ = [(k, C.c_void_p) for k in ("reference_kf", "local_mp", "n_local_mp", "n_to_match", "status", "kp_begin",
+                                          "mp_begin", "kp_claimed", "mp_valid", "mp_proj", "mp_view_cos", "mp_level",
+                                          "mp_desc", "mp_has_obs", "votes")]
+
+
 SIGNATURES = {
     "orbx_create": (C.c_int, [C.POINTER(OrbxParams), C.c_int, C.POINTER(VP)]),
     "orbx_destroy": (C.c_int, [VP]),
@@ -352,6 +374,8 @@ SIGNATURES = {
     "orbdb_detect_reloc": (C.c_int, [VP, C.POINTER(OrbdbQueryBatch), C.POINTER(OrbdbResult)]),
     "orbdb_detect_loop": (C.c_int, [VP, C.POINTER(OrbdbQueryBatch), C.POINTER(OrbdbResult)]),
     "orbdb_read_slots": (C.c_int, [VP, VP, VP]),
+    "orbtl_track_local_map_device": (C.c_int, [C.POINTER(OrbtlMap), C.POINTER(OrbtlFrames), C.POINTER(OrbtlResult), VP]),
+    "orbtl_track_local_map": (C.c_int, [C.POINTER(OrbtlMap), C.POINTER(OrbtlFrames), C.POINTER(OrbtlResult), C.c_int]),
     "orbx_pack_descriptors": (C.c_int,[VP, C.c_int, VP, VP, C.c_int, VP, C.c_int, VP]),
     "orbx_profile_enable": (C.c_int, [VP, C.c_int]),
     "orbx_profile_read": (C.c_int, [VP, VP, VP]),

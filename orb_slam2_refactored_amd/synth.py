@@ -1408,3 +1408,133 @@ def make_keyframe_db_case(seed: int = 0, max_keyframes: int = 70, n_add: int = 6
                 place=place, covis=covis, n_queries=Q, q_cap=q_cap, q_bow_word=qw, q_bow_weight=qv, q_n_words=qn, q_frame=q_frame,
                 q_place=q_place, conn_off=np.asarray(conn_off, np.int32), conn_idx=np.asarray(conn_idx, np.int32),
                 cov_off=np.asarray(cov_off, np.int32), cov_idx=np.asarray(cov_idx, np.int32))
+
+
+def local_map_tables(kf_mappoint, kf_n, n_mappoints: int, kf_bad=None, mp_bad=None, parent=None):
+    """The dependent tables of a local map from kf_mappoint (K, kf_cap) / kf_n: observations that agree with it (mp_obs_off /
+    mp_obs_kf ascending, mp_nobs), covisibility rows by shared-point count (descending, ties to the lower slot, at most 10,
+    -1 padded), a spanning tree (parent = the earlier keyframe sharing most points, slot k - 1 when none does; `parent`
+    overrides) and its children as a CSR with ascending lists."""
+    kf_mappoint = np.ascontiguousarray(kf_mappoint, np.int32)
+    K, M = kf_mappoint.shape[0], int(n_mappoints)
+    sees = np.zeros((K, M), bool)
+    for k in range(K):
+        row = kf_mappoint[k, :kf_n[k]]
+        sees[k, row[row >= 0]] = True
+    obs = [np.flatnonzero(sees[:, p]) for p in range(M)]
+    shared = sees.astype(np.int32) @ sees.astype(np.int32).T
+    np.fill_diagonal(shared, 0)
+    covis = np.full((K, 10), -1, np.int32)
+    par = np.full(K, -1, np.int32)
+    for k in range(K):
+        order = sorted((j for j in range(K) if shared[k, j] > 0), key=lambda j: (-shared[k, j], j))[:10]
+        covis[k, :len(order)] = order
+        if k > 0:
+            par[k] = int(np.argmax(shared[k, :k])) if shared[k, :k].max() > 0 else k - 1
+    if parent is not None:
+        par = np.asarray(parent, np.int32)
+    kids = [np.flatnonzero(par == k) for k in range(K)]
+    csr = lambda rows: (np.concatenate([[0], np.cumsum([len(r) for r in rows])]).astype(np.int32),  # noqa: E731
+                        (np.concatenate(rows) if rows and sum(len(r) for r in rows) else np.zeros(0)).astype(np.int32))
+    child_off, child_idx = csr(kids)
+    obs_off, obs_kf = csr(obs)
+    return dict(kf_bad=np.zeros(K, np.uint8) if kf_bad is None else np.asarray(kf_bad, np.uint8), kf_covis=covis, kf_parent=par,
+                kf_child_off=child_off, kf_child_idx=child_idx, kf_n=np.asarray(kf_n, np.int32), kf_mappoint=kf_mappoint,
+                mp_bad=np.zeros(M, np.uint8) if mp_bad is None else np.asarray(mp_bad, np.uint8),
+                mp_nobs=np.array([len(r) for r in obs], np.int32), mp_obs_off=obs_off, mp_obs_kf=obs_kf)
+
+
+def _lm_pose(x: float, yaw: float) -> np.ndarray:
+    c, s = np.cos(yaw), np.sin(yaw)
+    R = np.array([[c, 0, -s], [0, 1, 0], [s, 0, c]])
+    return np.concatenate([R.reshape(-1), -R @ np.array([x, 0.0, 0.0])]).astype(np.float32)
+
+
+def _lm_project(P, cam, xw):
+    """float64 projection of points xw (n, 3): u, v, z, dist to the camera centre."""
+    R, t = P[:9].astype(np.float64).reshape(3, 3), P[9:].astype(np.float64)
+    xc = xw.astype(np.float64) @ R.T + t
+    z = xc[:, 2]
+    with np.errstate(all="ignore"):
+        u, v = cam[0] * xc[:, 0] / z + cam[2], cam[1] * xc[:, 1] / z + cam[3]
+    return u, v, z, np.linalg.norm(xw - (-R.T @ t), axis=1)
+
+
+def make_local_map(seed: int = 0, n_keyframes: int = 70, kf_cap: int = 96, n_mappoints: int = 700, n_frames: int = 3,
+                   kp_cap: int = 160, step: float = 0.35, bad_frac: float = 0.05, matched=(5, 60, 120), n_levels: int = 8,
+                   scale_factor: float = 1.2, width: float = 640.0, height: float = 480.0):
+    """A consistent map as orbtl_map's slot tables plus a batch of frames (orbtl_frames) with keypoint arrays of stride
+    kp_cap for the projection search behind it.  Keyframes stand along the x axis `step` apart and look down +z at points
+    in a slab; frame f stands among them with matched[f % len(matched)] of its keypoints holding map points (a few bad, a
+    few without observations, one held twice, a few lying on another point's projection with its descriptor).  No (frame, point) pair has log(maxDistance / dist) / logScaleFactor within
+    1e-4 of an integer.  Returns (tables, frames, keypoints)."""
+    rng = np.random.default_rng(seed)
+    K, M, F = n_keyframes, n_mappoints, n_frames
+    cam = np.array([500.0, 500.0, width / 2, height / 2, 40.0], np.float32)
+    span = step * (K - 1)
+    xw = np.stack([rng.uniform(-3.0, span + 3.0, M), rng.uniform(-2.0, 2.0, M), rng.uniform(4.0, 12.0, M)], 1).astype(np.float32)
+    kf_pose = [_lm_pose(step * k, rng.uniform(-0.1, 0.1)) for k in range(K)]
+    kf_mappoint, kf_n = np.full((K, kf_cap), -1, np.int32), np.zeros(K, np.int32)
+    for k in range(K):
+        u, v, z, _ = _lm_project(kf_pose[k], cam, xw)
+        vis = np.flatnonzero((z > 0) & (u >= 0) & (u < width) & (v >= 0) & (v < height))
+        kf_n[k] = n = int(rng.integers(kf_cap // 2, kf_cap + 1))
+        take = rng.permutation(vis)[:int(0.8 * n)]
+        kf_mappoint[k, rng.permutation(n)[:len(take)]] = take
+    t = local_map_tables(kf_mappoint, kf_n, M, kf_bad=rng.random(K) < bad_frac, mp_bad=rng.random(M) < bad_frac)
+    log_sf = np.float32(np.log(scale_factor))
+    first = np.array([t["mp_obs_kf"][t["mp_obs_off"][p]] if t["mp_nobs"][p] else rng.integers(K) for p in range(M)])
+    centre = np.stack([[step * k, 0.0, 0.0] for k in first])
+    d_ref = np.linalg.norm(xw - centre, axis=1)
+    maxd = d_ref * scale_factor ** rng.integers(0, n_levels, M)
+    normal = (xw - centre) / d_ref[:, None] + rng.normal(0, 0.35, (M, 3))
+    normal /= np.linalg.norm(normal, axis=1, keepdims=True)
+    pose = np.stack([_lm_pose(rng.uniform(0.1, 0.9) * span, rng.uniform(-0.15, 0.15)) for _ in range(F)])
+    for _ in range(50):   # keep every (frame, point) scale off the integers
+        mm = np.stack([maxd, maxd / scale_factor ** (n_levels - 1)], 1).astype(np.float32)
+        gap = np.inf
+        for f in range(F):
+            e = np.log(mm[:, 0].astype(np.float64) / _lm_project(pose[f], cam, xw)[3]) / float(log_sf)
+            close = np.abs(e - np.round(e)) < 1e-4
+            maxd[close] *= 1.003
+            gap = min(gap, np.abs(e - np.round(e)).min())
+        if gap >= 1e-4:
+            break
+    t.update(mp_xw=xw, mp_normal=normal.astype(np.float32), mp_max_min=mm,
+             mp_desc=rng.integers(0, 256, (M, 32), dtype=np.uint8), mp_visible=rng.integers(0, 50, M).astype(np.int32))
+    frame_n = rng.integers(kp_cap * 3 // 4, kp_cap + 1, F).astype(np.int32)
+    frame_mp = np.full((F, kp_cap), -1, np.int32)
+    kp_xy = np.stack([rng.uniform(0, width, (F, kp_cap)), rng.uniform(0, height, (F, kp_cap))], 2).astype(np.float32)
+    kp_octave = rng.integers(0, n_levels, (F, kp_cap)).astype(np.int32)
+    kp_desc = rng.integers(0, 256, (F, kp_cap, 32), dtype=np.uint8)
+    for f in range(F):
+        u, v, z, dist = _lm_project(pose[f], cam, xw)
+        vis = rng.permutation(np.flatnonzero((z > 0) & (u >= 1) & (u < width - 1) & (v >= 1) & (v < height - 1)))
+        n, nm = int(frame_n[f]), min(int(matched[f % len(matched)]), len(vis), int(frame_n[f]) - 1)
+        slots = rng.permutation(n)
+        frame_mp[f, slots[:nm]] = vis[:nm]
+        if nm:
+            frame_mp[f, slots[nm]] = vis[0]   # one point held by two keypoints
+        src = np.concatenate([vis[:nm], vis[:1], rng.permutation(vis)[:max(n - nm - 1 - n // 5, 0)]])   # the rest stay random
+        wrong = min(6, nm, max(len(vis) - nm, 0))
+        src[:wrong] = vis[nm:nm + wrong]      # a few held points' keypoints lie on another point: that one finds them claimed
+        who = slots[:len(src)]
+        kp_xy[f, who] = np.stack([u[src], v[src]], 1) + rng.normal(0, 0.4, (len(src), 2))
+        lvl = np.ceil(np.log(t["mp_max_min"][src, 0] / dist[src]) / float(log_sf))
+        kp_octave[f, who] = np.clip(lvl - rng.integers(0, 2, len(src)), 0, n_levels - 1)
+        flips = rng.random((len(src), 256)) < 0.04
+        kp_desc[f, who] = t["mp_desc"][src] ^ np.packbits(flips, axis=1)
+    kp_xy = np.clip(kp_xy, 0, [width - 1e-3, height - 1e-3]).astype(np.float32)
+    with np.errstate(all="ignore"):
+        kp_uright = np.where(rng.random((F, kp_cap)) < 0.5, -1.0, kp_xy[..., 0] - rng.uniform(1, 9, (F, kp_cap))).astype(np.float32)
+    n_old = rng.integers(0, 4, F).astype(np.int32)
+    cap = K + 8
+    local_kf = np.full((F, cap), -1, np.int32)
+    for f in range(F):
+        local_kf[f, :n_old[f]] = rng.permutation(K)[:n_old[f]]
+    frames = dict(frame_n=frame_n, frame_mappoint=frame_mp, pose=pose.astype(np.float32), camera=np.tile(cam, (F, 1)),
+                  bounds=np.tile(np.array([0, width, 0, height], np.float32), (F, 1)), local_kf=local_kf, n_local_kf=n_old,
+                  n_levels=n_levels, log_scale_factor=float(log_sf), min_view_cos=0.5)
+    keypoints = dict(kp_xy=kp_xy, kp_octave=kp_octave, kp_uright=kp_uright, kp_desc=kp_desc, bounds=frames["bounds"],
+                     scale_factors=(np.float32(scale_factor) ** np.arange(n_levels)).astype(np.float32))
+    return t, frames, keypoints
