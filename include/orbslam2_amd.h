@@ -852,6 +852,105 @@ int orbba_optimize_sim3(const orbba_sim3_batch* in, orbba_sim3_result* out, int 
 int orbba_optimize_sim3_device(const orbba_sim3_batch* in, orbba_sim3_result* out, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * void Optimizer::OptimizeEssentialGraph(Map* map, KeyFrame* loopKF, KeyFrame* currKF, const KeyFrameAndPose&
+ * nonCorrectedSim3, const KeyFrameAndPose& correctedSim3, const LoopConnections& loopConnections, bool fixScale)
+ * (include/Optimizer.h, src/Optimizer.cc:743-942; LoopClosing::CorrectLoop) on slot tables: slot k is the k-th
+ * keyframe that is not bad, in map->GetAllKeyFrames() order.
+ * Vertices (:761-796): one VertexSim3Expmap per slot, estimate ToG2OSim3(vertex_sim3[k]) (:183-188: widened, the
+ * rotation through Quaterniond(R)), where vertex_sim3[k] is the keyframe's correctedSim3 entry or Sim3(pose) with
+ * scale 1 (the reference's nonCorrectedScw table).  fixed_slot (loopKF) is fixed; _fix_scale = fix_scale.
+ * Edges (:798-903): EdgeSim3 with information I7, vertex 0 = edge_i, vertex 1 = edge_j, in the reference's
+ * insertion order (orbba_essential_graph_edges builds the list).  Measurement Sji = Sjw * Swi in the float Sim3
+ * class (include/Sim3.h:40-63), then ToG2OSim3; both ends read vertex_sim3 when edge_table[e] == 0 (loop
+ * connections) and edge_sim3 otherwise (edge_sim3[k]: the nonCorrectedSim3 entry, or the vertex_sim3 row).
+ * Error log(C * v1 * v2^-1) (types_seven_dof_expmap.h:106-114, sim3.h:148-230 with its four branches, W.lu() as
+ * a partially pivoted LU); Jacobians by g2o's central differences at delta = 1e-9
+ * (base_binary_edge.hpp:131-205), so under fix_scale every scale column is exactly 0.
+ * Solver: BlockSolver_7_3 with nothing marginalised, so each trial solves the dense (H + lambda I) x = b of the
+ * active free vertices (a slot with no edge is never activated and keeps its estimate) by an unpivoted blocked
+ * LDL^T (a zero or non-finite pivot rejects the trial); Levenberg with lambda0 = 1e-16 (Optimizer.cc:749),
+ * optimize(20), no robust kernel, the rho / nu / ten-trial / nBad rules of orbba_local_ba.  chi2, H and b are
+ * summed edge by edge in insertion order without atomics: two runs are bit-identical.
+ * Recovery (:911-941): pose[k] = (R, (1. / s) * t) of FromG2OSim3(estimate) with the product in double; a point
+ * with point_ref[p] = r >= 0 becomes (correctedSwc[r] * vertex_sim3[r]).Map(P) in float; point_ref = -1 (a bad
+ * point) copies the point.  point_ref is correctedReference where correctedByKF == currKF->id, else the
+ * reference keyframe.  UpdateNormalAndDepth is not part of this call.
+ * Size: the system is dense, 7 ORBBA_EG_MAX_KEYFRAMES unknowns at most (103 MB for H, as much for its factor);
+ * a larger map is refused. */
+#define ORBBA_EG_MAX_KEYFRAMES 512
+#define ORBBA_EG_MAX_TRIALS 200   /* 20 iterations x 10 trials */
+
+typedef struct orbba_essential_graph {
+    int32_t        n_keyframes;
+    const float*   vertex_sim3;  /* n_keyframes x 13: R (row-major 3x3), t, s of the vertex table */
+    const float*   edge_sim3;    /* n_keyframes x 13: the edge-side table */
+    int32_t        fixed_slot;   /* loopKF */
+    int32_t        fix_scale;
+    int32_t        n_edges;
+    const int32_t* edge_i;       /* n_edges: vertex 0 */
+    const int32_t* edge_j;       /* n_edges: vertex 1 */
+    const uint8_t* edge_table;   /* n_edges: 0 = both ends from vertex_sim3, 1 = from edge_sim3 */
+    int32_t        n_points;
+    const float*   points;       /* n_points x 3 */
+    const int32_t* point_ref;    /* n_points: reference slot, -1 = skip */
+} orbba_essential_graph;
+
+typedef struct orbba_essential_graph_result {
+    double*  sim3_g2o;     /* n_keyframes x 8: q (x, y, z, w), t, s of the optimised vertices */
+    float*   pose;         /* n_keyframes x 12: Rcw (row-major 3x3) then tcw */
+    float*   points;       /* n_points x 3 */
+    double*  measurement;  /* n_edges x 8: the edges' measurements as g2o holds them; may be NULL */
+    int32_t* iterations;   /* 2: LM iterations run, trials run */
+    double*  chi2;         /* 1: the final chi2 */
+    uint8_t* accept;       /* ORBBA_EG_MAX_TRIALS: 1 = the trial was accepted, in order; the rest 0 */
+} orbba_essential_graph_result;
+
+/* Host entry: every pointer is host memory, synchronous.  ORB_EINVAL before any device call for null pointers,
+ * n_keyframes < 1 or > ORBBA_EG_MAX_KEYFRAMES, fixed_slot out of range, edge_i == edge_j, an index out of range
+ * (edges, point_ref < -1 or >= n_keyframes), a scale <= 0 and non-finite input. */
+int orbba_optimize_essential_graph(const orbba_essential_graph* in, orbba_essential_graph_result* out, int device);
+/* Device entry: every array in HBM; enqueue only on `stream`, nothing is copied back.  Sizes, fixed_slot and
+ * null pointers are checked; an edge whose indices are out of range or equal is left out of the graph and a
+ * point_ref out of range copies its point.  The workspace (the control struct, H, its factor) belongs to the calling
+ * thread and is reused by its next call: calls from one thread must be stream-ordered (the same stream, or an
+ * event between them); threads are independent of each other. */
+int orbba_optimize_essential_graph_device(const orbba_essential_graph* in, orbba_essential_graph_result* out,
+                                          void* stream);
+
+/* orbba_optimize_essential_graph with the device time of each kernel, summed over its launches, in kernel_ms
+ * (ORBBA_EG_KERNELS floats: setup, measure, linearize, assemble, begin, stage, solve, update, chi, ctl, recover).
+ * An event pair and a wait surround every launch, so the call itself is slower; for tools/time_essential_graph.py. */
+#define ORBBA_EG_KERNELS 11
+int orbba_essential_graph_profile(const orbba_essential_graph* in, orbba_essential_graph_result* out, int device,
+                                  float* kernel_ms);
+
+/* The edge list of Optimizer.cc:798-903 from slot tables (host only, no device call).  Loop connections first
+ * (:802-828, edge_table 0), in the order given: connection c is keyframe conn_kf[c] with the keyframes
+ * conn_slot[conn_begin[c] .. conn_begin[c + 1]); one is kept if it is (curr_slot, loop_slot) or its covisibility
+ * weight is >= min_weight, and enters insertedEdges.  Then per slot in order (:831-903, edge_table 1): the
+ * spanning-tree edge to parent[k] (-1: none), the loop edges with a smaller kf_id, and the covisibility row
+ * (GetCovisiblesByWeight order) with weight >= min_weight, leaving out the parent, a child (a slot whose parent
+ * is k), a loop edge, a slot of -1 (bad), a kf_id not smaller than the keyframe's and a pair in insertedEdges.
+ * Writes at most `capacity` edges and always the full count to *n_edges. */
+typedef struct orbba_eg_tables {
+    int32_t        n_keyframes;
+    const int32_t* kf_id;        /* n_keyframes: KeyFrame::id */
+    const int32_t* parent;       /* n_keyframes: slot or -1 */
+    const int32_t* loop_begin;   /* n_keyframes + 1 */
+    const int32_t* loop_slot;    /* GetLoopEdges() in iteration order */
+    const int32_t* covis_begin;  /* n_keyframes + 1 */
+    const int32_t* covis_slot;   /* the ordered connected keyframes; -1 for a bad one */
+    const int32_t* covis_weight;
+    int32_t        n_connections;
+    const int32_t* conn_kf;      /* n_connections */
+    const int32_t* conn_begin;   /* n_connections + 1 */
+    const int32_t* conn_slot;
+    int32_t        curr_slot, loop_kf_slot;
+} orbba_eg_tables;
+int orbba_essential_graph_edges(const orbba_eg_tables* g, int32_t min_weight, int32_t capacity, int32_t* edge_i,
+                                int32_t* edge_j, uint8_t* edge_table, int32_t* n_edges);
+
+/* ------------------------------------------------------------------------------------------
  * Sim3Solver(keyframe1, keyframe2, matches, fixScale), SetRansacParameters(probability, minInliers,
  * maxIterations) and bool Sim3Solver::iterate(int maxk, Sim3& sim3, std::vector<bool>& isInlier)
  * (include/Sim3Solver.h, src/Sim3Solver.cc:206-365; LoopClosing::FindLoopInCandidateKFs, LoopClosing.cc:105-135:

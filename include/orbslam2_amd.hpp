@@ -7,6 +7,7 @@
 //   ORB_SLAM2_AMD::LocalBundleAdjustment <- Optimizer::LocalBundleAdjustment (include/Optimizer.h:47)
 //   ORB_SLAM2_AMD::PoseOptimization      <- Optimizer::PoseOptimization (include/Optimizer.h:49)
 //   ORB_SLAM2_AMD::Optimizer::OptimizeSim3 <- Optimizer::OptimizeSim3 (src/Optimizer.cc:944-1100)
+//   ORB_SLAM2_AMD::Optimizer::OptimizeEssentialGraph <- Optimizer::OptimizeEssentialGraph (src/Optimizer.cc:743-942)
 //   ORB_SLAM2_AMD::SearchByProjection    <- ORBmatcher::SearchByProjection(Frame&, vector<MapPoint*>, th)
 //   ORB_SLAM2_AMD::ORBVocabulary         <- DBoW2 ORBVocabulary (include/ORBVocabulary.h) transform
 // Plain-type overloads are always available; when OpenCV is on the include path the
@@ -490,6 +491,46 @@ struct Optimizer {
         std::copy(thinned.begin(), thinned.begin() + b.total_kp1, match12.begin());
         std::copy(out_s12, out_s12 + 13, s12);
         return n;
+    }
+    // void Optimizer::OptimizeEssentialGraph(Map*, KeyFrame* loopKF, KeyFrame* currKF, nonCorrectedSim3,
+    // correctedSim3, loopConnections, bool fixScale) (src/Optimizer.cc:743-942; LoopClosing::CorrectLoop) on the slot
+    // tables of orbba_essential_graph in HBM.  Enqueue only: r.sim3_g2o, r.pose and r.points are what :911-941 write
+    // back, r.iterations / r.chi2 / r.accept the Levenberg trace.
+    static void OptimizeEssentialGraphDevice(const orbba_essential_graph& g, orbba_essential_graph_result& r,
+                                             void* stream = nullptr) {
+        check(orbba_optimize_essential_graph_device(&g, &r, stream), "orbba_optimize_essential_graph_device");
+    }
+    // The same on host arrays: pose (n_keyframes x 12) and points (n_points x 3, in / out) as SetPose and SetWorldPos
+    // receive them; returns the iterations run.
+    static int OptimizeEssentialGraph(orbba_essential_graph g, std::vector<float>& pose, std::vector<float>& points,
+                                      int device = 0) {
+        if (points.size() < 3 * static_cast<size_t>(std::max(g.n_points, 0)))
+            throw std::invalid_argument("OptimizeEssentialGraph: points is short");
+        pose.assign(12 * static_cast<size_t>(std::max(g.n_keyframes, 0)), 0.f);
+        std::vector<double> g2o(8 * static_cast<size_t>(std::max(g.n_keyframes, 0)));
+        std::vector<float> moved(std::max<size_t>(points.size(), 1));
+        std::vector<uint8_t> accept(ORBBA_EG_MAX_TRIALS);
+        int32_t it[2] = {0, 0};
+        double chi2 = 0;
+        g.points = points.data();
+        orbba_essential_graph_result r = {g2o.data(), pose.data(), moved.data(), nullptr, it, &chi2, accept.data()};
+        check(orbba_optimize_essential_graph(&g, &r, device), "orbba_optimize_essential_graph");
+        std::copy(moved.begin(), moved.begin() + 3 * static_cast<size_t>(g.n_points), points.begin());
+        return it[0];
+    }
+    // The edge list of :798-903 from slot tables (host only): edge_i, edge_j and edge_table in insertion order.
+    static void EssentialGraphEdges(const orbba_eg_tables& t, std::vector<int32_t>& edge_i, std::vector<int32_t>& edge_j,
+                                    std::vector<uint8_t>& edge_table, int32_t min_weight = 100) {
+        int32_t n = 0;
+        check(orbba_essential_graph_edges(&t, min_weight, 0, nullptr, nullptr, nullptr, &n), "orbba_essential_graph_edges");
+        edge_i.assign(std::max(n, 1), 0);
+        edge_j.assign(std::max(n, 1), 0);
+        edge_table.assign(std::max(n, 1), 0);
+        check(orbba_essential_graph_edges(&t, min_weight, n, edge_i.data(), edge_j.data(), edge_table.data(), &n),
+              "orbba_essential_graph_edges");
+        edge_i.resize(n);
+        edge_j.resize(n);
+        edge_table.resize(n);
     }
 };
 

@@ -6,6 +6,8 @@ Host mirrors of the reference's interfaces (tiantianxuabc/ORB_SLAM2_Refactored):
   Optimizer.LocalBundleAdjustment <- include/Optimizer.h:47
   Optimizer.PoseOptimization      <- include/Optimizer.h:49
   Optimizer.OptimizeSim3          <- src/Optimizer.cc:944-1100
+  Optimizer.OptimizeEssentialGraph <- src/Optimizer.cc:743-942 (optimizer.OptimizeEssentialGraph,
+                                     optimize_essential_graph_device, essential_graph_edges)
   Sim3SolverIterate               <- include/Sim3Solver.h (src/Sim3Solver.cc)
   PnPsolverIterate                <- include/PnPsolver.h (src/PnPsolver.cc); its draw table is make_pnp_draws
                                      (F, D, 4); make_draws is the Sim3 solver's (F, D, 3)

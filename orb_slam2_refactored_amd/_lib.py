@@ -161,6 +161,29 @@ class OptSim3Result(C.Structure):
                 ("iterations", C.c_void_p)]
 
 
+class EssentialGraph(C.Structure):
+    """orbba_essential_graph (include/orbslam2_amd.h)."""
+    _fields_ = [("n_keyframes", C.c_int32), ("vertex_sim3", C.c_void_p), ("edge_sim3", C.c_void_p),
+                ("fixed_slot", C.c_int32), ("fix_scale", C.c_int32), ("n_edges", C.c_int32),
+                ("edge_i", C.c_void_p), ("edge_j", C.c_void_p), ("edge_table", C.c_void_p),
+                ("n_points", C.c_int32), ("points", C.c_void_p), ("point_ref", C.c_void_p)]
+
+
+class EssentialGraphResult(C.Structure):
+    """orbba_essential_graph_result (include/orbslam2_amd.h)."""
+    _fields_ = [("sim3_g2o", C.c_void_p), ("pose", C.c_void_p), ("points", C.c_void_p), ("measurement", C.c_void_p),
+                ("iterations", C.c_void_p), ("chi2", C.c_void_p), ("accept", C.c_void_p)]
+
+
+class EssentialGraphTables(C.Structure):
+    """orbba_eg_tables (include/orbslam2_amd.h)."""
+    _fields_ = [("n_keyframes", C.c_int32), ("kf_id", C.c_void_p), ("parent", C.c_void_p),
+                ("loop_begin", C.c_void_p), ("loop_slot", C.c_void_p),
+                ("covis_begin", C.c_void_p), ("covis_slot", C.c_void_p), ("covis_weight", C.c_void_p),
+                ("n_connections", C.c_int32), ("conn_kf", C.c_void_p), ("conn_begin", C.c_void_p),
+                ("conn_slot", C.c_void_p), ("curr_slot", C.c_int32), ("loop_kf_slot", C.c_int32)]
+
+
 class Sim3SolverBatch(C.Structure):
     """orb_sim3solver_batch (include/orbslam2_amd.h)."""
     _fields_ = [("n_pairs", C.c_int32), ("total_kp1", C.c_int32), ("total_kp2", C.c_int32),
@@ -345,6 +368,10 @@ SIGNATURES = {
     "orbba_pose_optimization_device": (C.c_int, [C.POINTER(PoseBatch), C.POINTER(PoseResult), VP]),
     "orbba_optimize_sim3": (C.c_int, [C.POINTER(OptSim3Batch), C.POINTER(OptSim3Result), C.c_int]),
     "orbba_optimize_sim3_device": (C.c_int, [C.POINTER(OptSim3Batch), C.POINTER(OptSim3Result), VP]),
+    "orbba_optimize_essential_graph": (C.c_int, [C.POINTER(EssentialGraph), C.POINTER(EssentialGraphResult), C.c_int]),
+    "orbba_optimize_essential_graph_device": (C.c_int, [C.POINTER(EssentialGraph), C.POINTER(EssentialGraphResult), VP]),
+    "orbba_essential_graph_profile": (C.c_int, [C.POINTER(EssentialGraph), C.POINTER(EssentialGraphResult), C.c_int, VP]),
+    "orbba_essential_graph_edges": (C.c_int, [C.POINTER(EssentialGraphTables), C.c_int32, C.c_int32, VP, VP, VP, VP]),
     "orb_sim3solver_iterate": (C.c_int, [C.POINTER(Sim3SolverBatch), C.POINTER(Sim3SolverResult), C.c_int]),
     "orb_sim3solver_iterate_device": (C.c_int, [C.POINTER(Sim3SolverBatch), C.POINTER(Sim3SolverResult), VP]),
     "orb_pnpsolver_iterate": (C.c_int, [C.POINTER(PnPSolverBatch), C.POINTER(PnPSolverResult), C.c_int]),

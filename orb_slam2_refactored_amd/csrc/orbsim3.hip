@@ -31,6 +31,7 @@
 
 #include "common.h"
 #include "se3.h"
+#include "sim3_g2o.h"
 #include "wave_sum.h"
 #include "world_to_camera.h"
 
@@ -66,100 +67,11 @@ struct S3Args {
     int32_t* slots;   // workspace, total_kp1: pair p's kept slots, compacted, at kp1_begin[p]
 };
 
-struct S3 { double q[4], t[3], s; };   // g2o::Sim3: r (x, y, z, w), t, s
-
 struct S3Corr { double X1[3], X2[3], z1[2], z2[2], w1, w2; };
 
 struct S3Cam { double f1[2], c1[2], f2[2], c2[2]; };
 
-// ---------------------------------------------------------------- g2o::Sim3 (types/sim3.h)
-// Sim3(const Vector7d& update), sim3.h:70-142
-__device__ __forceinline__ void s3_exp(const double* u, S3& out) {
-    const double w0 = u[0], w1 = u[1], w2 = u[2], sigma = u[6];
-    const double theta = sqrt((w0 * w0 + w1 * w1) + w2 * w2);
-    const double O[9] = {0, -w2, w1, w2, 0, -w0, -w1, w0, 0};
-    double O2[9];
-#pragma unroll
-    for (int i = 0; i < 3; i++)
-#pragma unroll
-        for (int j = 0; j < 3; j++)
-            O2[3 * i + j] = (O[3 * i] * O[j] + O[3 * i + 1] * O[3 + j]) + O[3 * i + 2] * O[6 + j];
-    const double s = exp(sigma);
-    const double eps = 0.00001;
-    double A, B, C, R[9];
-    if (fabs(sigma) < eps) {
-        C = 1;
-        if (theta < eps) {
-            A = 1. / 2.;
-            B = 1. / 6.;
-#pragma unroll
-            for (int i = 0; i < 9; i++) R[i] = ((i % 4 == 0 ? 1.0 : 0.0) + O[i]) + O2[i];
-        } else {
-            double sn, cs;
-            sincos(theta, &sn, &cs);
-            const double theta2 = theta * theta;
-            A = (1 - cs) / theta2;
-            B = (theta - sn) / (theta2 * theta);
-            const double ra = sn / theta, rb = (1 - cs) / (theta * theta);
-#pragma unroll
-            for (int i = 0; i < 9; i++) R[i] = ((i % 4 == 0 ? 1.0 : 0.0) + ra * O[i]) + rb * O2[i];
-        }
-    } else {
-        C = (s - 1) / sigma;
-        if (theta < eps) {
-            const double sigma2 = sigma * sigma;
-            A = ((sigma - 1) * s + 1) / sigma2;
-            B = ((0.5 * sigma2 - sigma + 1) * s) / (sigma2 * sigma);
-#pragma unroll
-            for (int i = 0; i < 9; i++) R[i] = ((i % 4 == 0 ? 1.0 : 0.0) + O[i]) + O2[i];
-        } else {
-            double sn, cs;
-            sincos(theta, &sn, &cs);
-            const double ra = sn / theta, rb = (1 - cs) / (theta * theta);
-#pragma unroll
-            for (int i = 0; i < 9; i++) R[i] = ((i % 4 == 0 ? 1.0 : 0.0) + ra * O[i]) + rb * O2[i];
-            const double a = s * sn, b = s * cs;
-            const double theta2 = theta * theta, sigma2 = sigma * sigma;
-            const double c = theta2 + sigma2;
-            A = (a * sigma + (1 - b) * theta) / (theta * c);
-            B = (C - ((b - 1) * sigma + a * theta) / c) * 1. / theta2;
-        }
-    }
-    const Q4 r = q_from_R(R);   // Quaterniond(R), not renormalised
-    out.q[0] = r.x; out.q[1] = r.y; out.q[2] = r.z; out.q[3] = r.w;
-    out.s = s;
-#pragma unroll
-    for (int i = 0; i < 3; i++) {   // t = W * upsilon, W = A Omega + B Omega^2 + C I
-        const double W0 = (A * O[3 * i] + B * O2[3 * i]) + C * (i == 0 ? 1.0 : 0.0);
-        const double W1 = (A * O[3 * i + 1] + B * O2[3 * i + 1]) + C * (i == 1 ? 1.0 : 0.0);
-        const double W2 = (A * O[3 * i + 2] + B * O2[3 * i + 2]) + C * (i == 2 ? 1.0 : 0.0);
-        out.t[i] = (W0 * u[3] + W1 * u[4]) + W2 * u[5];
-    }
-}
-
-// operator*, sim3.h:266-272
-__device__ __forceinline__ void s3_mul(const S3& a, const S3& b, S3& o) {
-    const double ax = a.q[0], ay = a.q[1], az = a.q[2], aw = a.q[3];
-    const double bx = b.q[0], by = b.q[1], bz = b.q[2], bw = b.q[3];
-    double rt[3];
-    q_rotate(a.q, b.t, rt);
-    const double q0 = aw * bx + ax * bw + ay * bz - az * by, q1 = aw * by + ay * bw + az * bx - ax * bz,
-                 q2 = aw * bz + az * bw + ax * by - ay * bx, q3 = aw * bw - ax * bx - ay * by - az * bz;
-    const double s = a.s * b.s;
-#pragma unroll
-    for (int i = 0; i < 3; i++) o.t[i] = a.s * rt[i] + a.t[i];
-    o.q[0] = q0; o.q[1] = q1; o.q[2] = q2; o.q[3] = q3;
-    o.s = s;
-}
-
-// inverse(), sim3.h:233-236
-__device__ __forceinline__ void s3_inverse(const S3& a, S3& o) {
-    const double m = -1. / a.s;
-    const double v[3] = {m * a.t[0], m * a.t[1], m * a.t[2]};
-    o.q[0] = -a.q[0]; o.q[1] = -a.q[1]; o.q[2] = -a.q[2]; o.q[3] = a.q[3];
-    q_rotate(o.q, v, o.t);
-    o.s = 1. / a.s;
-}
+// g2o::Sim3 itself (exp, *, inverse) is in sim3_g2o.h
 
 // cam_map(project(S.map(X))) subtracted from z: computeError of either edge
 // (types_seven_dof_expmap.h:74-88, :138-145, :160-167; se3_ops.hpp:49-55; sim3.h:144-146)

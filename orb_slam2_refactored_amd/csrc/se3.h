@@ -2,7 +2,20 @@
 // PoseOptimization.  Same operation order as the oracle (Eigen's quaternion formulas).
 #pragma once
 
+#if defined(__HIPCC__)
 #include <hip/hip_runtime.h>
+#else   // host-only builds of the headers that share this arithmetic (tests/native)
+#include <cmath>
+#ifndef __host__
+#define __host__
+#endif
+#ifndef __device__
+#define __device__
+#endif
+#ifndef __forceinline__
+#define __forceinline__ inline
+#endif
+#endif
 
 struct Q4 { double x, y, z, w; };
 
@@ -70,7 +83,7 @@ __host__ __device__ __forceinline__ void q_to_R(const double* q4, double* R) {  
     R[3] = txy + twz;       R[4] = 1 - (txx + tzz); R[5] = tyz - twx;
     R[6] = txz - twy;       R[7] = tyz + twx;       R[8] = 1 - (txx + tyy);
 }
-__device__ __forceinline__ void q_rotate(const double* q4, const double* v, double* o) {   // Eigen q*v
+__host__ __device__ __forceinline__ void q_rotate(const double* q4, const double* v, double* o) {   // Eigen q*v
     const double qx = q4[0], qy = q4[1], qz = q4[2], qw = q4[3];
     double uv[3] = {qy * v[2] - qz * v[1], qz * v[0] - qx * v[2], qx * v[1] - qy * v[0]};
     uv[0] += uv[0]; uv[1] += uv[1]; uv[2] += uv[2];

@@ -1,5 +1,5 @@
-"""Optimizer::LocalBundleAdjustment / PoseOptimization / OptimizeSim3 mirrors (include/Optimizer.h:47-56) over the
-gfx950 C-ABI.
+"""Optimizer::LocalBundleAdjustment / PoseOptimization / OptimizeSim3 / OptimizeEssentialGraph mirrors
+(include/Optimizer.h:47-56) over the gfx950 C-ABI.
 
 The reference's graph gathering (local KFs by covisibility, local MPs, fixed KFs; Optimizer.cc:493-537)
 operates on ORB-SLAM's pointer graph; callers flatten that into a `problem` dict (see
@@ -10,8 +10,8 @@ import ctypes as C
 
 import numpy as np
 
-from ._lib import (BAProblem, BAResult, OptSim3Batch, OptSim3Result, PoseBatch, PoseResult, check, lib, ptr, stream_ptr,
-                   tptr)
+from ._lib import (BAProblem, BAResult, EssentialGraph, EssentialGraphResult, EssentialGraphTables, OptSim3Batch,
+                   OptSim3Result, PoseBatch, PoseResult, check, lib, ptr, stream_ptr, tptr)
 
 
 def _need(arrays: dict, counts: dict, what: str):
@@ -203,3 +203,130 @@ def optimize_sim3_device(batch: dict, out: dict | None = None, stream=None) -> d
     res = OptSim3Result(*[tptr(out[k]) for k in ("s12", "s12_g2o", "match12", "n_inliers", "iterations")])
     check(lib().orbba_optimize_sim3_device(C.byref(sb), C.byref(res), stream_ptr(stream)), "orbba_optimize_sim3_device")
     return out
+
+
+EG_MAX_KEYFRAMES = 512   # ORBBA_EG_MAX_KEYFRAMES
+EG_MAX_TRIALS = 200      # ORBBA_EG_MAX_TRIALS
+EG_KERNELS = ("setup", "measure", "linearize", "assemble", "begin", "stage", "solve", "update", "chi", "ctl", "recover")
+
+# orbba_essential_graph arrays: name -> (dtype, rows, row width); V keyframe slots, E edges, N points
+_EG_KEYS = (("vertex_sim3", np.float32, "V", 13), ("edge_sim3", np.float32, "V", 13), ("edge_i", np.int32, "E", 1),
+            ("edge_j", np.int32, "E", 1), ("edge_table", np.uint8, "E", 1), ("points", np.float32, "N", 3),
+            ("point_ref", np.int32, "N", 1))
+
+
+def _eg_struct(graph, conv, V, E, N, what):
+    for k, _, _, _ in _EG_KEYS:
+        if graph.get(k) is None:
+            raise ValueError(f"{what}: {k} is required")
+    dims = {"V": V, "E": E, "N": N}
+    _need(graph, {k: dims[rows] * width for k, _, rows, width in _EG_KEYS}, what)
+    p = {k: conv(graph[k], dt) for k, dt, _, _ in _EG_KEYS}
+    return EssentialGraph(V, p["vertex_sim3"], p["edge_sim3"], int(graph["fixed_slot"]), int(bool(graph["fix_scale"])), E,
+                          p["edge_i"], p["edge_j"], p["edge_table"], N, p["points"], p["point_ref"])
+
+
+def _eg_dims(graph):
+    size = lambda a: a.size if isinstance(a, np.ndarray) else int(a.numel()) if hasattr(a, "numel") else int(np.size(a))   # noqa: E731
+    for k in ("vertex_sim3", "edge_i", "point_ref"):
+        if graph.get(k) is None:
+            raise ValueError(f"OptimizeEssentialGraph: {k} is required")
+    return size(graph["vertex_sim3"]) // 13, size(graph["edge_i"]), size(graph["point_ref"])
+
+
+def OptimizeEssentialGraph(graph: dict, device: int = 0, profile: bool = False) -> dict:
+    """void Optimizer::OptimizeEssentialGraph(map, loopKF, currKF, nonCorrectedSim3, correctedSim3, loopConnections,
+    fixScale) (src/Optimizer.cc:743-942; LoopClosing::CorrectLoop) on host arrays in the orbba_essential_graph layout
+    (include/orbslam2_amd.h): vertex_sim3 / edge_sim3 (V, 13), fixed_slot, fix_scale, edge_i / edge_j / edge_table (E;
+    essential_graph_edges builds them), points (N, 3), point_ref (N, -1 = skip).  Returns sim3_g2o (V, 8), pose (V, 12),
+    points (N, 3), measurement (E, 8), iterations, trials, chi2 and accept (the trials' accept flags, in order);
+    with profile=True also kernel_ms, the device time per kernel (EG_KERNELS)."""
+    V, E, N = _eg_dims(graph)
+    keep = []
+
+    def k(a, dt):
+        a = np.ascontiguousarray(a, dt)
+        keep.append(a)
+        return ptr(a)
+
+    eg = _eg_struct(graph, k, V, E, N, "OptimizeEssentialGraph")
+    out = dict(sim3_g2o=np.zeros((V, 8)), pose=np.zeros((V, 12), np.float32), points=np.zeros((max(N, 1), 3), np.float32),
+               measurement=np.zeros((max(E, 1), 8)))
+    it, chi2, acc = np.zeros(2, np.int32), np.zeros(1), np.zeros(EG_MAX_TRIALS, np.uint8)
+    res = EssentialGraphResult(ptr(out["sim3_g2o"]), ptr(out["pose"]), ptr(out["points"]), ptr(out["measurement"]), ptr(it),
+                               ptr(chi2), ptr(acc))
+    if profile:
+        ms = np.zeros(len(EG_KERNELS), np.float32)
+        check(lib().orbba_essential_graph_profile(C.byref(eg), C.byref(res), int(device), ptr(ms)), "orbba_essential_graph_profile")
+        out["kernel_ms"] = dict(zip(EG_KERNELS, ms.tolist()))
+    else:
+        check(lib().orbba_optimize_essential_graph(C.byref(eg), C.byref(res), int(device)), "orbba_optimize_essential_graph")
+    out["points"], out["measurement"] = out["points"][:N], out["measurement"][:E]
+    out.update(iterations=int(it[0]), trials=int(it[1]), chi2=float(chi2[0]), accept=acc[:int(it[1])].astype(bool))
+    return out
+
+
+def optimize_essential_graph_device(graph: dict, out: dict | None = None, stream=None) -> dict:
+    """Device form of OptimizeEssentialGraph: GPU tensors for the orbba_essential_graph arrays, host values for
+    fixed_slot and fix_scale; enqueues the whole optimisation on `stream` (default: torch's current stream) and
+    copies nothing back.  `out` may hold the output tensors sim3_g2o (V, 8) f64, pose (V, 12) f32, points (N, 3)
+    f32, measurement (E, 8) f64, iterations (2) i32 = (iterations, trials), chi2 (1) f64 and accept
+    (EG_MAX_TRIALS) u8.  An edge with an index out of range is left out of the graph."""
+    import torch
+    V, E, N = _eg_dims(graph)
+    for name, dt, _, _ in _EG_KEYS:
+        t = graph.get(name)
+        if t is not None and (t.dtype != getattr(torch, np.dtype(dt).name) or not t.is_contiguous() or not t.is_cuda):
+            raise ValueError(f"optimize_essential_graph_device: {name} must be a contiguous {np.dtype(dt).name} GPU tensor")
+    eg = _eg_struct(graph, lambda t, dt: tptr(t), V, E, N, "optimize_essential_graph_device")
+    out = dict(out or {})
+    dev = graph["vertex_sim3"].device
+    want = {"sim3_g2o": ((V, 8), torch.float64), "pose": ((V, 12), torch.float32), "points": ((max(N, 1), 3), torch.float32),
+            "measurement": ((max(E, 1), 8), torch.float64), "iterations": ((2,), torch.int32), "chi2": ((1,), torch.float64),
+            "accept": ((EG_MAX_TRIALS,), torch.uint8)}
+    for name, (shape, dt) in want.items():
+        out.setdefault(name, torch.empty(shape, dtype=dt, device=dev))
+        t = out[name]
+        if t.dtype != dt or not t.is_contiguous() or not t.is_cuda:
+            raise ValueError(f"optimize_essential_graph_device: out[{name!r}] must be a contiguous {dt} GPU tensor")
+    _need(out, {"sim3_g2o": 8 * V, "pose": 12 * V, "points": 3 * N, "measurement": 8 * E, "iterations": 2, "chi2": 1,
+                "accept": EG_MAX_TRIALS}, "optimize_essential_graph_device")
+    res = EssentialGraphResult(*[tptr(out[k]) for k in ("sim3_g2o", "pose", "points", "measurement", "iterations", "chi2", "accept")])
+    check(lib().orbba_optimize_essential_graph_device(C.byref(eg), C.byref(res), stream_ptr(stream)),
+          "orbba_optimize_essential_graph_device")
+    return out
+
+
+def essential_graph_edges(tables: dict, min_weight: int = 100):
+    """The edge list of Optimizer.cc:798-903 from slot tables (orbba_eg_tables in include/orbslam2_amd.h): kf_id (V),
+    parent (V, -1 = none), loop_edges and covisibles (V lists of slots; covisibles as (slot, weight) pairs in
+    GetCovisiblesByWeight order, slot -1 for a bad keyframe), loop_connections (a list of (slot, [slots]) in the
+    map's iteration order), curr_slot and loop_slot.  Children are the slots whose parent is the keyframe.  Returns
+    edge_i, edge_j (int32) and edge_table (uint8) in the reference's insertion order.  Host only."""
+    V = len(tables["kf_id"])
+
+    def rows(lists):
+        begin = np.zeros(len(lists) + 1, np.int32)
+        begin[1:] = np.cumsum([len(l) for l in lists])
+        return begin, [v for l in lists for v in l]
+
+    lb, ls = rows(tables["loop_edges"])
+    cb, cv = rows(tables["covisibles"])
+    nb, ns = rows([c[1] for c in tables["loop_connections"]])
+    if len(tables["parent"]) != V or len(lb) != V + 1 or len(cb) != V + 1:
+        raise ValueError("essential_graph_edges: parent, loop_edges and covisibles need one row per keyframe")
+    arr = lambda v, n=1: np.ascontiguousarray(np.asarray(v, np.int32).reshape(-1, n) if len(v) else np.zeros((0, n), np.int32))   # noqa: E731
+    cv2 = arr(cv, 2)
+    a = dict(kf_id=arr(tables["kf_id"]), parent=arr(tables["parent"]), lb=lb, ls=arr(ls), cb=cb,
+             cs=np.ascontiguousarray(cv2[:, 0]), cw=np.ascontiguousarray(cv2[:, 1]),
+             ck=arr([c[0] for c in tables["loop_connections"]]), nb=nb, ns=arr(ns))
+    t = EssentialGraphTables(V, ptr(a["kf_id"]), ptr(a["parent"]), ptr(a["lb"]), ptr(a["ls"]), ptr(a["cb"]), ptr(a["cs"]),
+                             ptr(a["cw"]), len(tables["loop_connections"]), ptr(a["ck"]), ptr(a["nb"]), ptr(a["ns"]),
+                             int(tables["curr_slot"]), int(tables["loop_slot"]))
+    n = np.zeros(1, np.int32)
+    check(lib().orbba_essential_graph_edges(C.byref(t), int(min_weight), 0, None, None, None, ptr(n)), "orbba_essential_graph_edges")
+    E = int(n[0])
+    ei, ej, et = np.zeros(max(E, 1), np.int32), np.zeros(max(E, 1), np.int32), np.zeros(max(E, 1), np.uint8)
+    check(lib().orbba_essential_graph_edges(C.byref(t), int(min_weight), E, ptr(ei), ptr(ej), ptr(et), ptr(n)),
+          "orbba_essential_graph_edges")
+    return ei[:E], ej[:E], et[:E]
