@@ -743,6 +743,116 @@ int orbba_local_ba(const orbba_problem* prob, orbba_result* res, const volatile 
                    int device);
 
 /* ------------------------------------------------------------------------------------------
+ * void Optimizer::BundleAdjustment(keyframes, mappoints, nIterations, stopFlag, loopKFId, robust)
+ * (include/Optimizer.h, src/Optimizer.cc:197-343), which Optimizer::GlobalBundleAdjustemnt (LoopClosing's GlobalBA
+ * thread, LoopClosing.cc:366: 10 iterations, not robust) and Tracking::CreateInitialMapMonocular (Tracking.cc:1136:
+ * 20 iterations, robust) call.  The problem is orbba_problem as it is: the caller flattens :212-294 in reference
+ * order, leaving out bad keyframes and the observations in a keyframe that is bad or has id > maxKFId; pose_fixed
+ * is id == 0.
+ * Edge typing, stereo_rule: under ORBBA_GBA_RULE_REFERENCE the reference's `if (ur)` (:253) is reproduced as it
+ * stands: an observation with ur != 0 (-1 or a real right coordinate alike) is a mono edge, and one with ur == 0.0
+ * exactly a stereo edge with measurement (u, v, 0).  ORBBA_GBA_RULE_LOCAL types as LocalBA does (ur < 0 => mono).
+ * Schedule: one optimize(n_iterations) over every edge at level 0, Huber on every edge (delta = sqrt(5.991) mono,
+ * sqrt(7.815) stereo) or on none, no outlier classification.  The kernels, the lambda / rho / nu / ten-trial / nBad
+ * rules and the stop-flag polling are orbba_local_ba's, and so is the calling thread's device context.
+ * n_iterations == 0 optimises nothing and still counts as run.  A stop flag set on entry gives ran = 0 (g2o's
+ * optimize() returns at once); the reference then still copies the unchanged estimates back, so the outputs are
+ * the inputs through SE3Quat and narrowed.
+ * Outputs: pose_R / pose_t / pose_q / points as orbba_result's; pose_f and points_f are FromSE3Quat / FromVector3d
+ * of the estimates (:157-181), element by element the float of the double outputs: what the caller stores as
+ * TcwGBA / posGBA (loopKFId != 0) or passes to SetPose / SetWorldPos.  point_included[p] = 0 for a point without
+ * an edge (notIncludedMP, :285-289): it never enters the system and keeps its position.  UpdateNormalAndDepth
+ * (:335) is not part of the call.  At most ORBBA_MAX_FREE_KEYFRAMES free keyframes.
+ * ---------------------------------------------------------------------------------------- */
+#define ORBBA_GBA_RULE_REFERENCE 0
+#define ORBBA_GBA_RULE_LOCAL 1
+
+typedef struct orbba_gba_options {
+    int32_t n_iterations;   /* optimize(nIterations): 0 .. 1000 */
+    int32_t robust;         /* Huber on every edge, or no robust kernel */
+    int32_t stereo_rule;    /* ORBBA_GBA_RULE_REFERENCE or ORBBA_GBA_RULE_LOCAL */
+} orbba_gba_options;
+
+typedef struct orbba_gba_result {
+    double*   pose_R;         /* n_poses x 9 (optimised; fixed poses unchanged) */
+    double*   pose_t;         /* n_poses x 3 */
+    double*   pose_q;         /* n_poses x 4 (x,y,z,w); may be NULL */
+    double*   points;         /* n_points x 3 */
+    float*    pose_f;         /* n_poses x 12: Rcw row-major then tcw, narrowed */
+    float*    points_f;       /* n_points x 3, narrowed */
+    uint8_t*  point_included; /* n_points: 0 = no edge */
+    double*   edge_chi2;      /* n_edges: final chi2 (may be NULL) */
+    int32_t   iterations;     /* LM iterations run */
+    int32_t   trials;         /* LM trials run */
+    double    chi2;           /* active robust chi2 at the end */
+    int32_t   ran;            /* 0: the stop flag was set on entry */
+} orbba_gba_result;
+
+/* ORB_EINVAL for null pointers, n_iterations or stereo_rule out of range and an edge that refers to a missing
+ * vertex.  stop_flag as in orbba_local_ba; may be NULL.  The call is orbba_local_ba's, so that entry's environment
+ * knobs and test hooks apply to it as well: ORBBA_STRUCT, ORBBA_SOLVE_THREADS, ORBBA_SOLVE_SIMD0,
+ * ORBBA_DEBUG_TIMING, ORBBA_DEBUG_SPEC_EARLY and ORBBA_DEBUG_STOP_AFTER_TRIALS, which ends the loop after that many
+ * trials (0: nothing is optimised and ran = 0). */
+int orbba_bundle_adjustment(const orbba_problem* prob, const orbba_gba_options* opt, orbba_gba_result* res,
+                            const volatile int32_t* stop_flag, int device);
+
+/* The reduced camera system of orbba_bundle_adjustment above 21 free keyframes is factored in HBM, by one workgroup
+ * (orbba_local_ba's path) or by a blocked LDL^T spread over the grid: per block column of 32 one launch for the
+ * diagonal block and the panel and one for the trailing update, then both substitutions.  ORBBA_GBA_SOLVE=grid or
+ * =single (environment, read per call) forces a path; the default takes the grid from 64 free keyframes.  Both run
+ * every sum in a fixed order.  orbba_debug_ldlt_grid exposes the grid factorisation alone: A x = b for a dense
+ * symmetric A (D x D row-major, host memory, the lower triangle is read; 1 <= D <= 6 ORBBA_MAX_FREE_KEYFRAMES),
+ * synchronous; *ok = 0 for a zero or non-finite pivot, and x is then not written. */
+int orbba_debug_ldlt_grid(const double* A, const double* b, int D, double* x, int32_t* ok, int device);
+
+/* ------------------------------------------------------------------------------------------
+ * The map update behind the global bundle adjustment (GlobalBA::_Run, LoopClosing.cc:392-446) on slot tables that
+ * follow orbtl_map's conventions, so a device-resident map is corrected in place.
+ * Keyframes (:393-413): walked from the origins down the spanning tree.  A child whose flag is clear gets
+ * TcwGBA = (Tchild * Tparent^-1) * parent.TcwGBA, with both poses the ones from before the update (a keyframe's
+ * SetPose comes after its children were handled), and its flag is set.  Every keyframe the walk reaches then gets
+ * TcwBefGBA = its old pose and pose = TcwGBA.  One the walk never reaches keeps all three rows, a stale
+ * kf_pose_bef included, which the point pass may still read: the reference's behaviour.
+ * Points (:416-446): a bad point is skipped; one with mp_in_gba set takes mp_pos_gba; any other is skipped if its
+ * reference keyframe's flag is clear after the walk, and else goes into that keyframe's camera by TcwBefGBA and
+ * back out by the inverse of its new pose.
+ * The arithmetic is CameraPose's, in float (include/CameraPose.h:44-63): Inverse = (R^T, -R^T t), operator* is
+ * t = R1 t2 + t1, R = R1 R2, products summed in k = 0, 1, 2 order, no contraction.  A child's value depends on its
+ * parent's alone, so the device's level-by-level walk gives the sequential result bit for bit, in two launches
+ * whatever the tree's depth.
+ * ---------------------------------------------------------------------------------------- */
+typedef struct orbba_gba_map {
+    int32_t n_keyframes, n_mappoints, n_origins;
+    const int32_t* origins;        /* n_origins: map->keyFrameOrigins as slots */
+    const int32_t* kf_child_off;   /* n_keyframes + 1: CSR of GetChildren() (orbtl_map's) */
+    const int32_t* kf_child_idx;
+    uint8_t* kf_in_gba;            /* n_keyframes: BAGlobalForKF == loopKFId; read and updated */
+    float*   kf_pose;              /* n_keyframes x 12: Rcw row-major, tcw; read and updated (SetPose) */
+    float*   kf_pose_gba;          /* n_keyframes x 12: TcwGBA; read and updated */
+    float*   kf_pose_bef;          /* n_keyframes x 12: TcwBefGBA; read and updated */
+    const uint8_t* mp_bad;         /* n_mappoints */
+    const uint8_t* mp_in_gba;      /* n_mappoints: MapPoint::BAGlobalForKF == loopKFId */
+    const float*   mp_pos_gba;     /* n_mappoints x 3: posGBA */
+    const int32_t* mp_ref_kf;      /* n_mappoints: GetReferenceKeyFrame() as a slot */
+    float*   mp_xw;                /* n_mappoints x 3: read and updated (SetWorldPos) */
+} orbba_gba_map;
+
+/* Host entry: every pointer is host memory, synchronous; the five updated arrays are written back.  ORB_EINVAL
+ * before any device call for null pointers, negative sizes, a kf_child_off that does not start at 0 or decreases,
+ * an origin, child or (for a point that is neither bad nor in the adjustment) reference slot out of range, a slot
+ * that is an origin twice, a child of two parents or both an origin and a child, and a non-finite kf_pose row,
+ * flagged kf_pose_gba row or used mp_pos_gba row. */
+int orbba_gba_update_map(const orbba_gba_map* map, int device);
+/* Device entry: every array in HBM; enqueue only on `stream`, nothing is copied back.  Sizes and null pointers are
+ * checked.  Whatever the tables hold, the walk ends within n_keyframes levels and nothing is written out of bounds:
+ * an index out of range is skipped, a slot is visited once (so a cycle or a repeated child ends there) and a
+ * kf_child_off entry is clamped to [its predecessor's clamped value, kf_child_off[n_keyframes]].  kf_child_idx must
+ * hold kf_child_off[n_keyframes] entries; it may be NULL, and then no keyframe has a child.
+ * The workspace belongs to the calling thread and is reused by its next call: calls from one thread must be
+ * stream-ordered; threads are independent of each other. */
+int orbba_gba_update_map_device(const orbba_gba_map* map, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Motion-only bundle adjustment.  Replaces Optimizer::PoseOptimization (include/Optimizer.h:49,
  * src/Optimizer.cc:345-489) for a batch of frames: one SE3 vertex per frame, one unary
  * EdgeSE3ProjectXYZOnlyPose / EdgeStereoSE3ProjectXYZOnlyPose per matched map point

@@ -5,6 +5,8 @@
 //   ORB_SLAM2_AMD::ORBextractor   <- ORB_SLAM2::ORBextractor   (include/ORBextractor.h:35-81)
 //   ORB_SLAM2_AMD::ORBmatcher     <- ORB_SLAM2::ORBmatcher Hamming kernels (include/ORBmatcher.h)
 //   ORB_SLAM2_AMD::LocalBundleAdjustment <- Optimizer::LocalBundleAdjustment (include/Optimizer.h:47)
+//   ORB_SLAM2_AMD::BundleAdjustment, GlobalBAUpdateMap <- Optimizer::BundleAdjustment (src/Optimizer.cc:197-343) and
+//                                            the GlobalBA thread's map update (src/LoopClosing.cc:392-446)
 //   ORB_SLAM2_AMD::PoseOptimization      <- Optimizer::PoseOptimization (include/Optimizer.h:49)
 //   ORB_SLAM2_AMD::Optimizer::OptimizeSim3 <- Optimizer::OptimizeSim3 (src/Optimizer.cc:944-1100)
 //   ORB_SLAM2_AMD::Optimizer::OptimizeEssentialGraph <- Optimizer::OptimizeEssentialGraph (src/Optimizer.cc:743-942)
@@ -297,6 +299,27 @@ inline bool LocalBundleAdjustment(const orbba_problem& problem, orbba_result& re
                                   int device = 0) {
     check(orbba_local_ba(&problem, &result, stopFlag, device), "orbba_local_ba");
     return result.ran != 0;
+}
+
+// void Optimizer::BundleAdjustment(keyframes, mappoints, nIterations, stopFlag, loopKFId, robust)
+// (Optimizer.cc:197-343) from the flattened graph (:212-294, pose_fixed = (id == 0)), with the reference's edge
+// typing (`if (ur)`).  The caller writes result.pose_f / points_f to TcwGBA / posGBA and sets BAGlobalForKF
+// (loopKFId != 0) or calls SetPose / SetWorldPos (:296-342), leaving out the points with point_included == 0.
+// Returns false when the stop flag was set on entry.
+inline bool BundleAdjustment(const orbba_problem& problem, orbba_gba_result& result, int nIterations = 5,
+                             const volatile int32_t* stopFlag = nullptr, bool robust = true, int device = 0) {
+    const orbba_gba_options opt{nIterations, robust ? 1 : 0, ORBBA_GBA_RULE_REFERENCE};
+    check(orbba_bundle_adjustment(&problem, &opt, &result, stopFlag, device), "orbba_bundle_adjustment");
+    return result.ran != 0;
+}
+
+// The map update of the GlobalBA thread (LoopClosing.cc:392-446) on host tables, synchronous; the ...Device form
+// takes tables in HBM and only enqueues on `stream`.
+inline void GlobalBAUpdateMap(const orbba_gba_map& map, int device = 0) {
+    check(orbba_gba_update_map(&map, device), "orbba_gba_update_map");
+}
+inline void GlobalBAUpdateMapDevice(const orbba_gba_map& map, void* stream) {
+    check(orbba_gba_update_map_device(&map, stream), "orbba_gba_update_map_device");
 }
 
 // int Optimizer::PoseOptimization(Frame*) (include/Optimizer.h:49, src/Optimizer.cc:345-489) over a

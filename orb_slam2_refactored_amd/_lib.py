@@ -69,6 +69,25 @@ class BAResult(C.Structure):
                 ("iterations", C.c_int32 * 2), ("chi2", C.c_double * 2), ("ran", C.c_int32)]
 
 
+class GBAOptions(C.Structure):
+    """orbba_gba_options (include/orbslam2_amd.h)."""
+    _fields_ = [("n_iterations", C.c_int32), ("robust", C.c_int32), ("stereo_rule", C.c_int32)]
+
+
+class GBAResult(C.Structure):
+    """orbba_gba_result (include/orbslam2_amd.h)."""
+    _fields_ = [(k, C.c_void_p) for k in ("pose_R", "pose_t", "pose_q", "points", "pose_f", "points_f", "point_included",
+                                          "edge_chi2")] + [
+        ("iterations", C.c_int32), ("trials", C.c_int32), ("chi2", C.c_double), ("ran", C.c_int32)]
+
+
+class GBAMap(C.Structure):
+    """orbba_gba_map (include/orbslam2_amd.h)."""
+    _fields_ = [("n_keyframes", C.c_int32), ("n_mappoints", C.c_int32), ("n_origins", C.c_int32)] + [
+        (k, C.c_void_p) for k in ("origins", "kf_child_off", "kf_child_idx", "kf_in_gba", "kf_pose", "kf_pose_gba",
+                                  "kf_pose_bef", "mp_bad", "mp_in_gba", "mp_pos_gba", "mp_ref_kf", "mp_xw")]
+
+
 class ProjBatch(C.Structure):
     _fields_ = [("n_frames", C.c_int32), ("total_kp", C.c_int32), ("total_mp", C.c_int32),
                 ("kp_begin", C.c_void_p), ("kp_xy", C.c_void_p), ("kp_octave", C.c_void_p), ("kp_uright", C.c_void_p),
@@ -364,6 +383,10 @@ SIGNATURES = {
                                  C.POINTER(C.c_int)]),
     "orbv_transform_batch_device": (C.c_int, [VP, VP, VP, C.c_int, C.c_int, C.c_int, VP, VP, VP, VP, VP, VP, VP, VP]),
     "orbba_local_ba": (C.c_int, [C.POINTER(BAProblem), C.POINTER(BAResult), VP, C.c_int]),
+    "orbba_bundle_adjustment": (C.c_int, [C.POINTER(BAProblem), C.POINTER(GBAOptions), C.POINTER(GBAResult), VP, C.c_int]),
+    "orbba_debug_ldlt_grid": (C.c_int, [VP, VP, C.c_int, VP, VP, C.c_int]),
+    "orbba_gba_update_map": (C.c_int, [C.POINTER(GBAMap), C.c_int]),
+    "orbba_gba_update_map_device": (C.c_int, [C.POINTER(GBAMap), VP]),
     "orbba_pose_optimization": (C.c_int, [C.POINTER(PoseBatch), C.POINTER(PoseResult), C.c_int]),
     "orbba_pose_optimization_device": (C.c_int, [C.POINTER(PoseBatch), C.POINTER(PoseResult), VP]),
     "orbba_optimize_sim3": (C.c_int, [C.POINTER(OptSim3Batch), C.POINTER(OptSim3Result), C.c_int]),

@@ -169,6 +169,7 @@ struct BAOptions {
                          // that each loop's first guesses miss and the fallback paths run
     bool solve256;       // ORBBA_SOLVE_THREADS=256: the LDS solve's round-5 workgroup instead of 1024 threads
     int simd0_helpers;   // ORBBA_SOLVE_SIMD0=1: wavefront 0's SIMD-mates take trailing tiles too
+    std::string gba_solve;   // ORBBA_GBA_SOLVE: "grid" / "single" force BundleAdjustment's HBM solve path
     bool try_counts() const { return smode != "host" && smode != "sorted" && smode != "generic"; }
 };
 BAOptions read_options() {
@@ -185,6 +186,8 @@ BAOptions read_options() {
     o.spec_slack = num("ORBBA_DEBUG_SPEC_EARLY", 0) != 0 ? 1 : 0;
     o.solve256 = num("ORBBA_SOLVE_THREADS", 0) == 256;
     o.simd0_helpers = num("ORBBA_SOLVE_SIMD0", 0) != 0 ? 1 : 0;
+    const char* gs = getenv("ORBBA_GBA_SOLVE");
+    o.gba_solve = gs ? gs : "";
     return o;
 }
 
@@ -203,7 +206,33 @@ struct PhaseTimer {
 };
 
 constexpr int LOOKAHEAD = 2;     // LM steps kept enqueued ahead of the host (= control snapshot ring slots)
-constexpr int NEXT_ITERS = 10;   // the second optimize()'s iterations (Optimizer.cc:672)
+
+// What a call runs on the problem: the optimize() calls, the robust kernels they start with, the edge typing
+// and whether the outliers are classified (between two optimize() calls and into edge_outlier at the end).
+struct BASchedule {
+    int loops;          // optimize() calls: 1 or 2
+    int iters[2];       // their iterations
+    int robust;         // the edges' robust-kernel flag at the start (Huber, delta by edge type)
+    int stereo_rule;    // ORBBA_GBA_RULE_LOCAL: ur < 0 => mono (Optimizer.cc:595); _REFERENCE: `if (ur)` (:253)
+    bool classify;      // levels + robust kernels off between the loops, edge_outlier at the end
+    bool grid_solve;    // a reduced system in HBM may be factored over the grid (ldlt_grid.h; ORBBA_GBA_SOLVE)
+};
+// Free keyframes from which the grid-wide factorisation is the default (the smallest measured size at
+// which it beats the single workgroup by more than the run-to-run spread)
+constexpr int GBA_GRID_MIN_FREE_KEYFRAMES = 64;
+// LocalBundleAdjustment: optimize(5), classify, optimize(10) (Optimizer.cc:636-672)
+constexpr BASchedule LOCAL_BA_SCHEDULE{2, {5, 10}, 1, ORBBA_GBA_RULE_LOCAL, true, false};
+
+// Where a call's results go (orbba_result's and orbba_gba_result's common part).
+struct BAOutputs {
+    double *pose_R, *pose_t, *pose_q, *points;
+    uint8_t* edge_outlier;   // null without a classification
+    double* edge_chi2;
+    int32_t iterations[2] = {0, 0};
+    double chi2[2] = {0, 0};
+    int32_t trials = 0;      // LM trials over the whole call
+    int32_t ran = 0;
+};
 
 // One optimize()'s loop as the host sees it.
 struct LoopState {
@@ -222,7 +251,8 @@ struct LoopState {
 // One orbba_local_ba call.
 struct LocalBACall {
     const orbba_problem* pr;
-    orbba_result* res;
+    BAOutputs* res;
+    const BASchedule sch;
     const volatile int32_t* stop_flag;
     const int device, P, N, E;
     BAContext& C;
@@ -254,6 +284,8 @@ struct LocalBACall {
     bool have_classified = false;   // the outlier classification ran (second optimize())
     // the solve of this call's system (plan_solve)
     bool glob = false;   // reduced system in HBM (ba_solve_global_kernel)
+    bool grid = false;   // ... and factored over the grid (ldlt_grid.h), BundleAdjustment only
+    LdltGrid lg{};
     int D = 0, Dp = 0;
     size_t ldlt_lds = 0;
     dim3 gg;                     // the point kernels' grid: 8 lanes per point
@@ -265,16 +297,17 @@ struct LocalBACall {
     bool hook_stopped = false;    // the device ended a loop on the stop flag (or the test hook)
     int spec_launched[2] = {0, 0};   // speculative loop ends enqueued per loop (ORBBA_DEBUG_TIMING report)
 
-    LocalBACall(const orbba_problem* pr_, orbba_result* res_, const volatile int32_t* stop_, int device_, BAContext& C_,
-                HostStructure& hs_)
-        : pr(pr_), res(res_), stop_flag(stop_), device(device_), P(pr_->n_poses), N(pr_->n_points), E(pr_->n_edges),
+    LocalBACall(const orbba_problem* pr_, BAOutputs* res_, const BASchedule& sch_, const volatile int32_t* stop_,
+                int device_, BAContext& C_, HostStructure& hs_)
+        : pr(pr_), res(res_), sch(sch_), stop_flag(stop_), device(device_), P(pr_->n_poses), N(pr_->n_points), E(pr_->n_edges),
           C(C_), hs(hs_) {}
 
     bool stopped() const { return stop_flag && *stop_flag; }
 
     int validate() {
         ORB_CHECK_ARG(P >= 0 && N >= 0 && E >= 0, "negative sizes");
-        ORB_CHECK_ARG(res->pose_R && res->pose_t && res->points && res->edge_outlier, "null result buffers");
+        ORB_CHECK_ARG(res->pose_R && res->pose_t && res->points && (res->edge_outlier || !sch.classify),
+                      "null result buffers");
         tm.mark("entry");
         for (int e = 0; e < E; e++)
             ORB_CHECK_ARG(pr->edge_point[e] >= 0 && pr->edge_point[e] < N && pr->edge_pose[e] >= 0 &&
@@ -326,7 +359,10 @@ struct LocalBACall {
         std::memcpy(h.fixed, pr->pose_fixed, P);
         std::memcpy(h.ep, pr->edge_point, 4 * (size_t)E);
         std::memcpy(h.ek, pr->edge_pose, 4 * (size_t)E);
-        for (int e = 0; e < E; e++) h.stereo[e] = pr->edge_obs[3 * e + 2] < 0 ? 0 : 1;   // ur < 0 => mono (:595)
+        if (sch.stereo_rule == ORBBA_GBA_RULE_LOCAL)
+            for (int e = 0; e < E; e++) h.stereo[e] = pr->edge_obs[3 * e + 2] < 0 ? 0 : 1;   // ur < 0 => mono (:595)
+        else   // `if (ur)` (:253): any non-zero ur, -1 included, is a mono edge; ur == 0 a stereo edge (u, v, 0)
+            for (int e = 0; e < E; e++) h.stereo[e] = pr->edge_obs[3 * e + 2] != 0 ? 0 : 1;
         std::memcpy(h.obs, pr->edge_obs, 24 * (size_t)E);
         std::memcpy(h.info, pr->edge_inv_sigma2, 8 * (size_t)E);
         std::memcpy(h.cam, pr->edge_cam, 8 * (one_cam ? 5 : 5 * (size_t)E));
@@ -346,7 +382,7 @@ struct LocalBACall {
         // (the control block is written whole by the first optimize()'s fill: trials / stopped count from 0
         // over the whole call)
         ORB_HIP_TRY(hipMemcpyAsync(C.prob.ptr, C.h_prob.ptr, up_bytes, hipMemcpyHostToDevice, st));
-        if ((rc = fills.add(s.robust, E, 1, st)) || (rc = fills.add(s.level, E, 0, st)) ||
+        if ((rc = fills.add(s.robust, E, sch.robust ? 1 : 0, st)) || (rc = fills.add(s.level, E, 0, st)) ||
             (rc = fills.add(s.err, 24 * (size_t)E, 0, st)))
             return rc;
         res->iterations[0] = res->iterations[1] = 0;
@@ -396,6 +432,8 @@ struct LocalBACall {
             set_error("LocalBA: more than ORBBA_MAX_FREE_KEYFRAMES free keyframes in the local window");
             return ORB_EINVAL;
         }
+        grid = glob && sch.grid_solve &&
+               (opt.gba_solve == "grid" || (opt.gba_solve != "single" && hs.np >= GBA_GRID_MIN_FREE_KEYFRAMES));
         Dp = solve_dp(D);
         ldlt_lds = glob ? (size_t)3 * Dp * 8 : std::max<size_t>(solve_lds_doubles(D) * 8, 16);
         gg = dim3((hs.nl * 8 + 63) / 64);
@@ -408,7 +446,7 @@ struct LocalBACall {
         const size_t nblk = hs.blk_i1.size();
         const SystemDims d{(size_t)hs.n_act, (size_t)hs.np, (size_t)hs.nl, nblk,
                            (size_t)(SB_SPLIT + 1) * (glob ? 36 * nblk : (size_t)D * D),   // + Hpp part
-                           glob ? (size_t)Dp * (Dp + 1) : 0};
+                           glob ? (grid ? ldlt_grid_doubles(D) : (size_t)Dp * (Dp + 1)) : 0};
         SystemLayout y;
         int rc;
         if ((rc = C.sys.reserve(y.carve(nullptr, d)))) return rc;
@@ -417,6 +455,7 @@ struct LocalBACall {
         b.S = y.S; b.Spart = y.Spart; b.blk_done = y.blk_done; b.bs = y.bs; b.x = y.x; b.rchi = y.rchi;
         b.part = y.part; b.Sg = y.Sg;
         d_wgpart = y.wgpart;
+        if (grid) lg = ldlt_grid_carve(b.Sg, D, &b.ctl->done);
         if (!fresh) return ORB_OK;
         // (J needs no clearing: every linearising trial writes the entries that are read -- those of the
         // edges to free poses, zeros for a level-1 edge.  S / the part matrices are zero where no pose
@@ -513,7 +552,11 @@ struct LocalBACall {
         }
         hipLaunchKernelGGL(ba_schur_block_kernel, dim3(b.nblk + 1 + b.np, SB_SPLIT), dim3(1024), 0, st, b, D,
                            L.enq == 0 ? 0 : 1, glob ? 0 : 1);
-        if (glob) hipLaunchKernelGGL(ba_solve_global_kernel, dim3(1), dim3(1024), ldlt_lds, st, b, D);
+        if (grid) {
+            ldlt_grid_enqueue_stage(lg, b.S, b.bs, st);
+            ldlt_grid_enqueue_factor(lg, st);
+            hipLaunchKernelGGL(ba_solve_grid_finish_kernel, dim3(1), dim3(1024), (size_t)lg.Dg * 8, st, b, lg, D);
+        } else if (glob) hipLaunchKernelGGL(ba_solve_global_kernel, dim3(1), dim3(1024), ldlt_lds, st, b, D);
         else if (opt.solve256) hipLaunchKernelGGL(ba_solve_kernel<256>, dim3(1), dim3(256), ldlt_lds, st, b, D, 1);
         else hipLaunchKernelGGL(ba_solve_kernel<1024>, dim3(1), dim3(1024), ldlt_lds, st, b, D, opt.simd0_helpers);
         const int slot = L.enq % LOOKAHEAD;
@@ -547,7 +590,7 @@ struct LocalBACall {
             classify_levels(1);
             if (!stop_flag && opt.stop_after < 0) {
                 // (seq: the second loop's step 0)
-                hipLaunchKernelGGL(ba_ctl_start_kernel, dim3(1), dim3(1), 0, st, b, NEXT_ITERS, 1, C.d_ring + 0,
+                hipLaunchKernelGGL(ba_ctl_start_kernel, dim3(1), dim3(1), 0, st, b, sch.iters[1], 1, C.d_ring + 0,
                                    C.next_seq(), 1);
                 L.trans_spec = true;
             }
@@ -640,6 +683,7 @@ struct LocalBACall {
         if ((rc = run_loop(L))) return rc;
         res->iterations[which] = L.last.iters_done;
         res->chi2[which] = L.last.chi_out;
+        res->trials = L.last.trials;
         hook_stopped = hook_stopped || L.last.stopped;
         return ORB_OK;
     }
@@ -658,8 +702,10 @@ struct LocalBACall {
         h.carve(C.h_res.ptr, P, N, E);
         std::memcpy(res->pose_t, h.t, 24 * (size_t)P);
         std::memcpy(res->points, h.X, 24 * (size_t)N);
-        if (ran) std::memcpy(res->edge_outlier, h.outlier, E);
-        else std::memset(res->edge_outlier, 0, E);
+        if (res->edge_outlier) {
+            if (ran) std::memcpy(res->edge_outlier, h.outlier, E);
+            else std::memset(res->edge_outlier, 0, E);
+        }
         if (res->edge_chi2) std::memcpy(res->edge_chi2, h.chi2, 8 * (size_t)E);
         for (int i = 0; i < P; i++) {
             q_to_R(&h.q[4 * i], res->pose_R + 9 * i);
@@ -695,31 +741,72 @@ struct LocalBACall {
         const bool ran = !stopped() && opt.stop_after != 0;   // Optimizer.cc:633-634: stop before optimising => nothing done
         res->ran = ran ? 1 : 0;
         if (ran) {
-            if ((rc = optimize(5, 0, false))) return rc;
-            if (!stopped() && !hook_stopped) {   // doMore (:639-642)
+            if ((rc = optimize(sch.iters[0], 0, sch.loops == 1))) return rc;
+            if (sch.loops == 2 && !stopped() && !hook_stopped) {   // doMore (:639-642)
                 // tag outliers (level 1) and drop the robust kernels (:644-670)
                 // (no host copy of the levels: the structure is not rebuilt and the device counts the
                 // level-0 edges for ba_ctl_start_kernel)
-                if (E) {
+                if (E && sch.classify) {
                     if (!leveled) classify_levels(0);
                     ORB_HIP_TRY(hipGetLastError());
                     have_classified = true;
                 }
                 tm.mark("classify enqueued");
-                if ((rc = optimize(NEXT_ITERS, 1, true))) return rc;
+                if ((rc = optimize(sch.iters[1], 1, true))) return rc;
             }
         }
         return finish(ran);
     }
 };
 
+thread_local HostStructure g_hs;   // capacity kept across calls
+
+
 }  // namespace
 
 extern "C" int orbba_local_ba(const orbba_problem* pr, orbba_result* res, const volatile int32_t* stop_flag,
                               int device) {
     ORB_CHECK_ARG(pr && res, "null argument");
-    thread_local HostStructure hs;   // capacity kept across calls
-    return LocalBACall(pr, res, stop_flag, device, g_ba, hs).run();
+    BAOutputs o{res->pose_R, res->pose_t, res->pose_q, res->points, res->edge_outlier, res->edge_chi2};
+    const int rc = LocalBACall(pr, &o, LOCAL_BA_SCHEDULE, stop_flag, device, g_ba, g_hs).run();
+    for (int k = 0; k < 2; k++) {
+        res->iterations[k] = o.iterations[k];
+        res->chi2[k] = o.chi2[k];
+    }
+    res->ran = o.ran;
+    return rc;
+}
+
+// Optimizer::BundleAdjustment (Optimizer.cc:197-343): one optimize(n_iterations) over every edge, no
+// classification; the same call, context and kernels as LocalBA under another schedule.
+extern "C" int orbba_bundle_adjustment(const orbba_problem* pr, const orbba_gba_options* op, orbba_gba_result* res,
+                                       const volatile int32_t* stop_flag, int device) {
+    ORB_CHECK_ARG(pr && op && res, "null argument");
+    ORB_CHECK_ARG(op->n_iterations >= 0 && op->n_iterations <= 1000, "n_iterations out of range");
+    ORB_CHECK_ARG(op->stereo_rule == ORBBA_GBA_RULE_REFERENCE || op->stereo_rule == ORBBA_GBA_RULE_LOCAL,
+                  "unknown stereo_rule");
+    ORB_CHECK_ARG(res->pose_f && res->points_f && res->point_included, "null result buffers");
+    ORB_CHECK_ARG(pr->n_edges <= 0 || pr->edge_point, "null edge_point");
+    const BASchedule sch{1, {op->n_iterations, 0}, op->robust ? 1 : 0, op->stereo_rule, false, true};
+    BAOutputs o{res->pose_R, res->pose_t, res->pose_q, res->points, nullptr, res->edge_chi2};
+    res->iterations = res->trials = res->ran = 0;
+    res->chi2 = 0;
+    if (int rc = LocalBACall(pr, &o, sch, stop_flag, device, g_ba, g_hs).run()) return rc;
+    res->iterations = o.iterations[0];
+    res->trials = o.trials;
+    res->chi2 = o.chi2[0];
+    res->ran = o.ran;
+    // FromSE3Quat / FromVector3d (Optimizer.cc:157-181): the estimates narrowed element by element
+    const int P = pr->n_poses, N = pr->n_points;
+    for (int i = 0; i < P; i++) {
+        for (int k = 0; k < 9; k++) res->pose_f[12 * i + k] = (float)res->pose_R[9 * i + k];
+        for (int k = 0; k < 3; k++) res->pose_f[12 * i + 9 + k] = (float)res->pose_t[3 * i + k];
+    }
+    for (size_t k = 0; k < 3 * (size_t)N; k++) res->points_f[k] = (float)res->points[k];
+    // notIncludedMP (:285-289): a point without an edge never enters the system and keeps its position
+    std::memset(res->point_included, 0, N);
+    for (int e = 0; e < pr->n_edges; e++) res->point_included[pr->edge_point[e]] = 1;
+    return ORB_OK;
 }
 
 extern "C" int orbba_debug_stamps(unsigned long long* out) {
@@ -732,4 +819,32 @@ extern "C" int orbba_debug_stamps(unsigned long long* out) {
     set_error("built without ORB_BA_STAMPS");
     return ORB_EINVAL;
 #endif
+}
+
+// ldlt_grid.h alone: (A + 0) x = b for a dense symmetric A (D x D, row-major; the lower triangle is read), host
+// memory, synchronous.  *ok = 0: a zero or non-finite pivot, x is not written.
+extern "C" int orbba_debug_ldlt_grid(const double* A, const double* b, int D, double* x, int32_t* ok, int device) {
+    ORB_CHECK_ARG(A && b && x && ok, "null argument");
+    ORB_CHECK_ARG(D >= 1 && D <= 6 * ORBBA_MAX_FREE_KEYFRAMES, "D out of range");
+    ORB_HIP_TRY(hipSetDevice(device));
+    DevBuf in, ws;
+    struct Free {
+        DevBuf &a, &b;
+        ~Free() { a.release(); b.release(); }
+    } fr{in, ws};
+    int rc;
+    const size_t nA = (size_t)D * D;
+    if ((rc = in.reserve((nA + D) * 8)) || (rc = ws.reserve(ldlt_grid_doubles(D) * 8))) return rc;
+    ORB_HIP_TRY(hipMemcpy(in.ptr, A, nA * 8, hipMemcpyHostToDevice));
+    ORB_HIP_TRY(hipMemcpy(in.as<double>() + nA, b, (size_t)D * 8, hipMemcpyHostToDevice));
+    const LdltGrid g = ldlt_grid_carve(ws.as<double>(), D, nullptr);
+    ldlt_grid_enqueue_stage(g, in.as<double>(), in.as<double>() + nA, nullptr);
+    ldlt_grid_enqueue_factor(g, nullptr);
+    hipLaunchKernelGGL(ldlt_grid_solve_kernel, dim3(1), dim3(1024), (size_t)g.Dg * 8, nullptr, g);
+    ORB_HIP_TRY(hipGetLastError());
+    int okv = 0;
+    ORB_HIP_TRY(hipMemcpy(&okv, g.ok, 4, hipMemcpyDeviceToHost));
+    *ok = okv;
+    if (okv) ORB_HIP_TRY(hipMemcpy(x, g.y, (size_t)D * 8, hipMemcpyDeviceToHost));
+    return ORB_OK;
 }

@@ -3,6 +3,7 @@
 #pragma once
 
 #include "ldlt_blocked.h"
+#include "ldlt_grid.h"
 #include "orbba_dev.h"
 
 namespace orbamd {
@@ -331,6 +332,37 @@ __global__ __launch_bounds__(1024) void ba_solve_global_kernel(BADev b, int D) {
     if (tid == 0) b.ctl->ok2 = ok;
     const double lam = b.ctl->lambda;
     for (int i = tid; i < b.np; i += blockDim.x) {   // push() + oplus, scale terms x.(lambda x + b)
+        const int id = b.ps_id[i];
+        double q[4], t[3], xi[6], part = 0;
+        for (int j = 0; j < 4; j++) q[j] = b.q[4 * id + j];
+        for (int j = 0; j < 3; j++) t[j] = b.t[3 * id + j];
+        for (int j = 0; j < 6; j++) {
+            xi[j] = ok ? y[6 * i + j] : 0.0;
+            part += xi[j] * (lam * xi[j] + b.bp[6 * i + j]);
+        }
+        b.part[b.nl + i] = part;
+        for (int j = 0; j < 4; j++) b.q_sv[4 * id + j] = q[j];
+        for (int j = 0; j < 3; j++) b.t_sv[3 * id + j] = t[j];
+        se3_exp_update(xi, q, t);
+        for (int j = 0; j < 4; j++) b.q[4 * id + j] = q[j];
+        for (int j = 0; j < 3; j++) b.t[3 * id + j] = t[j];
+    }
+}
+
+// The end of an LM trial's solve on the grid path: both substitutions on the factor ldlt_grid.h left, then what
+// ba_solve_global_kernel does behind its own: x, ok2, push() + oplus of the free poses and their scale terms.
+__global__ __launch_bounds__(1024) void ba_solve_grid_finish_kernel(BADev b, LdltGrid g, int D) {
+    BA_RETURN_IF_DONE(b);
+    extern __shared__ __attribute__((aligned(16))) double ysh[];
+    const int tid = threadIdx.x;
+    const int ok = *g.ok;
+    if (ok) ldlt_grid_substitute(g, ysh);
+    __syncthreads();
+    const double* y = ysh;
+    for (int i = tid; i < D; i += blockDim.x) b.x[i] = ok ? y[i] : 0.0;
+    if (tid == 0) b.ctl->ok2 = ok;
+    const double lam = b.ctl->lambda;
+    for (int i = tid; i < b.np; i += blockDim.x) {
         const int id = b.ps_id[i];
         double q[4], t[3], xi[6], part = 0;
         for (int j = 0; j < 4; j++) q[j] = b.q[4 * id + j];

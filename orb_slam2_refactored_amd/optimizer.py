@@ -1,5 +1,5 @@
-"""Optimizer::LocalBundleAdjustment / PoseOptimization / OptimizeSim3 / OptimizeEssentialGraph mirrors
-(include/Optimizer.h:47-56) over the gfx950 C-ABI.
+"""Optimizer::LocalBundleAdjustment / BundleAdjustment / PoseOptimization / OptimizeSim3 / OptimizeEssentialGraph
+mirrors (include/Optimizer.h:40-56) and the GlobalBA thread's map update over the gfx950 C-ABI.
 
 The reference's graph gathering (local KFs by covisibility, local MPs, fixed KFs; Optimizer.cc:493-537)
 operates on ORB-SLAM's pointer graph; callers flatten that into a `problem` dict (see
@@ -10,8 +10,8 @@ import ctypes as C
 
 import numpy as np
 
-from ._lib import (BAProblem, BAResult, EssentialGraph, EssentialGraphResult, EssentialGraphTables, OptSim3Batch,
-                   OptSim3Result, PoseBatch, PoseResult, check, lib, ptr, stream_ptr, tptr)
+from ._lib import (BAProblem, BAResult, EssentialGraph, EssentialGraphResult, EssentialGraphTables, GBAMap, GBAOptions,
+                   GBAResult, OptSim3Batch, OptSim3Result, PoseBatch, PoseResult, check, lib, ptr, stream_ptr, tptr)
 
 
 def _need(arrays: dict, counts: dict, what: str):
@@ -23,9 +23,8 @@ def _need(arrays: dict, counts: dict, what: str):
             raise ValueError(f"{what}: {name} has {n} elements, needs {want}")
 
 
-def LocalBundleAdjustment(problem: dict, stop_flag=None, device: int = 0) -> dict:
-    keep = []
-
+def _ba_problem(problem: dict, keep: list, what: str) -> BAProblem:
+    """orbba_problem over the dict's arrays (kept alive in `keep`), after the shape checks."""
     def k(a, dt):
         a = np.ascontiguousarray(a, dt)
         keep.append(a)
@@ -33,28 +32,126 @@ def LocalBundleAdjustment(problem: dict, stop_flag=None, device: int = 0) -> dic
 
     P0, N0, E0 = len(problem["pose_R"]), len(problem["points"]), len(problem["edge_point"])
     _need(problem, {"pose_R": 9 * P0, "pose_t": 3 * P0, "pose_fixed": P0, "points": 3 * N0, "edge_pose": E0,
-                    "edge_obs": 3 * E0, "edge_inv_sigma2": E0, "edge_cam": 5 * E0}, "LocalBundleAdjustment")
-    pr = BAProblem(len(problem["pose_R"]), k(problem["pose_R"], np.float64), k(problem["pose_t"], np.float64),
-                   k(problem["pose_fixed"], np.uint8), len(problem["points"]), k(problem["points"], np.float64),
-                   len(problem["edge_point"]), k(problem["edge_point"], np.int32), k(problem["edge_pose"], np.int32),
-                   k(problem["edge_obs"], np.float64), k(problem["edge_inv_sigma2"], np.float64),
-                   k(problem["edge_cam"], np.float64))
+                    "edge_obs": 3 * E0, "edge_inv_sigma2": E0, "edge_cam": 5 * E0}, what)
+    return BAProblem(len(problem["pose_R"]), k(problem["pose_R"], np.float64), k(problem["pose_t"], np.float64),
+                     k(problem["pose_fixed"], np.uint8), len(problem["points"]), k(problem["points"], np.float64),
+                     len(problem["edge_point"]), k(problem["edge_point"], np.int32), k(problem["edge_pose"], np.int32),
+                     k(problem["edge_obs"], np.float64), k(problem["edge_inv_sigma2"], np.float64),
+                     k(problem["edge_cam"], np.float64))
+
+
+def _stop_flag_ptr(stop_flag, keep: list):
+    if stop_flag is None:
+        return None
+    flag = stop_flag if isinstance(stop_flag, C.c_int32) else C.c_int32(int(stop_flag))
+    keep.append(flag)
+    return C.cast(C.pointer(flag), C.c_void_p)
+
+
+def LocalBundleAdjustment(problem: dict, stop_flag=None, device: int = 0) -> dict:
+    keep = []
+    pr = _ba_problem(problem, keep, "LocalBundleAdjustment")
     P, N, E = pr.n_poses, pr.n_points, pr.n_edges
     # (np.empty: orbba_local_ba writes every element of each, also when it optimises nothing)
     out = dict(pose_R=np.empty((P, 9)), pose_t=np.empty((P, 3)), pose_q=np.empty((P, 4)), points=np.empty((N, 3)),
                edge_outlier=np.empty(E, np.uint8), edge_chi2=np.empty(E))
     res = BAResult(ptr(out["pose_R"]), ptr(out["pose_t"]), ptr(out["pose_q"]), ptr(out["points"]),
                    ptr(out["edge_outlier"]), ptr(out["edge_chi2"]))
-    sf = None
-    if stop_flag is not None:
-        flag = stop_flag if isinstance(stop_flag, C.c_int32) else C.c_int32(int(stop_flag))
-        keep.append(flag)
-        sf = C.cast(C.pointer(flag), C.c_void_p)
+    sf = _stop_flag_ptr(stop_flag, keep)
     check(lib().orbba_local_ba(C.byref(pr), C.byref(res), sf, device), "orbba_local_ba")
     out["iterations"] = tuple(res.iterations)
     out["chi2"] = tuple(res.chi2)
     out["ran"] = bool(res.ran)   # False: stop flag set on entry, nothing to write back (Optimizer.cc:633-634)
     return out
+
+
+GBA_STEREO_RULES = {"reference": 0, "local": 1}   # ORBBA_GBA_RULE_REFERENCE / ORBBA_GBA_RULE_LOCAL
+
+
+def BundleAdjustment(problem: dict, n_iterations: int = 5, robust: bool = True, stereo_rule: str = "reference",
+                     stop_flag=None, device: int = 0) -> dict:
+    """void Optimizer::BundleAdjustment(keyframes, mappoints, nIterations, stopFlag, loopKFId, robust)
+    (src/Optimizer.cc:197-343; GlobalBundleAdjustemnt and Tracking::CreateInitialMapMonocular) on the `problem` dict
+    of LocalBundleAdjustment, flattened from :212-294 with pose_fixed = (id == 0).  stereo_rule "reference" types
+    the edges by the reference's `if (ur)` (any non-zero ur is a mono edge), "local" as LocalBA does.  Returns
+    pose_R / pose_t / pose_q / points (float64), pose_f (P, 12) and points_f (N, 3) = what goes into TcwGBA / posGBA
+    or SetPose / SetWorldPos, point_included (N; 0 = no edge, position kept), edge_chi2, iterations, trials, chi2
+    and ran (False: the stop flag was set on entry)."""
+    if stereo_rule not in GBA_STEREO_RULES:
+        raise ValueError(f"BundleAdjustment: stereo_rule must be one of {sorted(GBA_STEREO_RULES)}")
+    keep = []
+    pr = _ba_problem(problem, keep, "BundleAdjustment")
+    P, N, E = pr.n_poses, pr.n_points, pr.n_edges
+    out = dict(pose_R=np.empty((P, 9)), pose_t=np.empty((P, 3)), pose_q=np.empty((P, 4)), points=np.empty((N, 3)),
+               pose_f=np.empty((P, 12), np.float32), points_f=np.empty((N, 3), np.float32),
+               point_included=np.empty(N, np.uint8), edge_chi2=np.empty(E))
+    res = GBAResult(*[ptr(out[k]) for k in ("pose_R", "pose_t", "pose_q", "points", "pose_f", "points_f",
+                                            "point_included", "edge_chi2")])
+    opt = GBAOptions(int(n_iterations), int(bool(robust)), GBA_STEREO_RULES[stereo_rule])
+    sf = _stop_flag_ptr(stop_flag, keep)
+    check(lib().orbba_bundle_adjustment(C.byref(pr), C.byref(opt), C.byref(res), sf, int(device)), "orbba_bundle_adjustment")
+    out.update(iterations=int(res.iterations), trials=int(res.trials), chi2=float(res.chi2), ran=bool(res.ran))
+    return out
+
+
+# orbba_gba_map arrays in struct order: name -> (dtype, rows, row width, updated); O origins, K keyframe slots,
+# K1 = K + 1, C children, M map points
+_GBA_MAP_KEYS = (("origins", np.int32, "O", 1, False), ("kf_child_off", np.int32, "K1", 1, False),
+                 ("kf_child_idx", np.int32, "C", 1, False), ("kf_in_gba", np.uint8, "K", 1, True),
+                 ("kf_pose", np.float32, "K", 12, True), ("kf_pose_gba", np.float32, "K", 12, True),
+                 ("kf_pose_bef", np.float32, "K", 12, True), ("mp_bad", np.uint8, "M", 1, False),
+                 ("mp_in_gba", np.uint8, "M", 1, False), ("mp_pos_gba", np.float32, "M", 3, False),
+                 ("mp_ref_kf", np.int32, "M", 1, False), ("mp_xw", np.float32, "M", 3, True))
+
+
+def _size(a):
+    return a.size if isinstance(a, np.ndarray) else int(a.numel()) if hasattr(a, "numel") else int(np.size(a))
+
+
+def _gba_map_dims(m: dict, what: str):
+    for k, _, _, _, _ in _GBA_MAP_KEYS:
+        if m.get(k) is None:
+            raise ValueError(f"{what}: {k} is required")
+    K, M = _size(m["kf_in_gba"]), _size(m["mp_bad"])
+    dims = {"O": _size(m["origins"]), "K": K, "K1": K + 1, "M": M}
+    _need(m, {k: dims[rows] * width for k, _, rows, width, _ in _GBA_MAP_KEYS if rows != "C"}, what)
+    return dims
+
+
+def GlobalBAUpdateMap(map: dict, device: int = 0) -> dict:
+    """The map update of the GlobalBA thread (LoopClosing.cc:392-446) on host arrays in the orbba_gba_map layout
+    (include/orbslam2_amd.h): origins, kf_child_off / kf_child_idx (GetChildren() as CSR), kf_in_gba, kf_pose,
+    kf_pose_gba, kf_pose_bef (K, 12), mp_bad, mp_in_gba, mp_pos_gba (M, 3), mp_ref_kf and mp_xw (M, 3).  Returns the
+    five updated arrays (kf_in_gba, kf_pose, kf_pose_gba, kf_pose_bef, mp_xw) as new arrays; the input is not
+    written."""
+    dims = _gba_map_dims(map, "GlobalBAUpdateMap")
+    arr = {}
+    for k, dt, rows, width, updated in _GBA_MAP_KEYS:
+        a = np.array(map[k], dt) if updated else np.ascontiguousarray(map[k], dt)   # (np.array copies)
+        arr[k] = np.ascontiguousarray(a)
+    off = arr["kf_child_off"]
+    dims["C"] = int(off[-1]) if len(off) else 0
+    _need(arr, {"kf_child_idx": max(dims["C"], 0)}, "GlobalBAUpdateMap")
+    gm = GBAMap(dims["K"], dims["M"], dims["O"], *[ptr(arr[k]) for k, _, _, _, _ in _GBA_MAP_KEYS])
+    check(lib().orbba_gba_update_map(C.byref(gm), int(device)), "orbba_gba_update_map")
+    K, M = dims["K"], dims["M"]
+    return dict(kf_in_gba=arr["kf_in_gba"].reshape(K), kf_pose=arr["kf_pose"].reshape(K, 12),
+                kf_pose_gba=arr["kf_pose_gba"].reshape(K, 12), kf_pose_bef=arr["kf_pose_bef"].reshape(K, 12),
+                mp_xw=arr["mp_xw"].reshape(M, 3))
+
+
+def global_ba_update_map_device(map: dict, stream=None) -> None:
+    """Device form of GlobalBAUpdateMap: GPU tensors for the orbba_gba_map arrays; enqueues two launches on `stream`
+    (default: torch's current stream), copies nothing back and updates kf_in_gba, kf_pose, kf_pose_gba, kf_pose_bef
+    and mp_xw in place.  kf_child_idx must hold kf_child_off[K] entries (not checked: that would be a copy back)."""
+    import torch
+    dims = _gba_map_dims(map, "global_ba_update_map_device")
+    for name, dt, _, _, _ in _GBA_MAP_KEYS:
+        t = map[name]
+        if not hasattr(t, "is_cuda") or t.dtype != getattr(torch, np.dtype(dt).name) or not t.is_contiguous() or not t.is_cuda:
+            raise ValueError(f"global_ba_update_map_device: {name} must be a contiguous {np.dtype(dt).name} GPU tensor")
+    gm = GBAMap(dims["K"], dims["M"], dims["O"], *[tptr(map[k]) for k, _, _, _, _ in _GBA_MAP_KEYS])
+    check(lib().orbba_gba_update_map_device(C.byref(gm), stream_ptr(stream)), "orbba_gba_update_map_device")
 
 
 def _pose_arrays(batch: dict):
