@@ -805,6 +805,22 @@ int orbba_bundle_adjustment(const orbba_problem* prob, const orbba_gba_options* 
  * synchronous; *ok = 0 for a zero or non-finite pivot, and x is then not written. */
 int orbba_debug_ldlt_grid(const double* A, const double* b, int D, double* x, int32_t* ok, int device);
 
+/* The other two solves alone, for tests: the kernels orbba_local_ba launches, on a fabricated problem without poses or
+ * points, so that only the solve of A x = b runs.  A is dense symmetric (D x D row-major, host memory; the lower
+ * triangle and the diagonal blocks are read), both calls are synchronous, allocate and free their own buffers and use
+ * no state of the thread's BA context.  *ok = 0 for a zero or non-finite pivot (a negative pivot is no failure), and x
+ * is then all zero.
+ * orbba_debug_ldlt_lds: the LDS kernel (up to 21 free keyframes), D even, 2 <= D <= 128, with `threads` = 1024 or 256
+ * (ORBBA_SOLVE_THREADS) and simd0_helpers = 0 or 1 (ORBBA_SOLVE_SIMD0).  That kernel sums the system from the Schur
+ * step's part matrices and adds lambda on the diagonal while it stages it; the entry splits A - lambda I into such
+ * parts, so the system solved is A for any lambda that can be taken off A's diagonal without rounding (0 always;
+ * ORB_EINVAL otherwise).
+ * orbba_debug_ldlt_hbm: the single-workgroup HBM kernel, 1 <= D <= 7 (ORBBA_EG_MAX_KEYFRAMES - 1): the factorisation
+ * orbba_optimize_essential_graph runs as well. */
+int orbba_debug_ldlt_lds(const double* A, const double* b, int D, double lambda, int threads, int simd0_helpers,
+                         double* x, int32_t* ok, int device);
+int orbba_debug_ldlt_hbm(const double* A, const double* b, int D, double* x, int32_t* ok, int device);
+
 /* ------------------------------------------------------------------------------------------
  * The map update behind the global bundle adjustment (GlobalBA::_Run, LoopClosing.cc:392-446) on slot tables that
  * follow orbtl_map's conventions, so a device-resident map is corrected in place.

@@ -385,6 +385,8 @@ SIGNATURES = {
     "orbba_local_ba": (C.c_int, [C.POINTER(BAProblem), C.POINTER(BAResult), VP, C.c_int]),
     "orbba_bundle_adjustment": (C.c_int, [C.POINTER(BAProblem), C.POINTER(GBAOptions), C.POINTER(GBAResult), VP, C.c_int]),
     "orbba_debug_ldlt_grid": (C.c_int, [VP, VP, C.c_int, VP, VP, C.c_int]),
+    "orbba_debug_ldlt_lds": (C.c_int, [VP, VP, C.c_int, C.c_double, C.c_int, C.c_int, VP, VP, C.c_int]),
+    "orbba_debug_ldlt_hbm": (C.c_int, [VP, VP, C.c_int, VP, VP, C.c_int]),
     "orbba_gba_update_map": (C.c_int, [C.POINTER(GBAMap), C.c_int]),
     "orbba_gba_update_map_device": (C.c_int, [C.POINTER(GBAMap), VP]),
     "orbba_pose_optimization": (C.c_int, [C.POINTER(PoseBatch), C.POINTER(PoseResult), C.c_int]),

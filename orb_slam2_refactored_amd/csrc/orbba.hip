@@ -248,6 +248,26 @@ struct LoopState {
     int remaining() const { return seen ? last.iters_max - last.it : iters; }
 };
 
+// The dynamic LDS limit is a process-wide attribute of a solve kernel: raised (a host call) only when a call needs
+// more than any call before it on this device, never lowered.  One table for every caller of these kernels (LocalBACall
+// and the debug entries at the end of this file).
+enum SolveKernel { SOLVE_LDS_1024 = 0, SOLVE_HBM = 1, SOLVE_LDS_256 = 2 };
+static int raise_solve_lds_limit(SolveKernel which, int device, size_t ldlt_lds) {
+    static std::mutex mu;
+    static size_t lim[64][3] = {};
+    const void* solve_fn = which == SOLVE_HBM       ? (const void*)ba_solve_global_kernel
+                           : which == SOLVE_LDS_256 ? (const void*)ba_solve_kernel<256>
+                                                    : (const void*)ba_solve_kernel<1024>;
+    const size_t need = std::max<size_t>(ldlt_lds, 1024);
+    std::lock_guard<std::mutex> lk(mu);
+    size_t& cur = lim[device & 63][which];
+    if (need > cur) {
+        ORB_HIP_TRY(hipFuncSetAttribute(solve_fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)need));
+        cur = need;
+    }
+    return ORB_OK;
+}
+
 // One orbba_local_ba call.
 struct LocalBACall {
     const orbba_problem* pr;
@@ -526,21 +546,8 @@ struct LocalBACall {
         return ORB_OK;
     }
 
-    // the dynamic LDS limit is a process-wide attribute of the kernel: raised (a host call) only
-    // when a call needs more than any call before it on this device, never lowered
     int raise_lds_limit() {
-        static std::mutex mu;
-        static size_t lim[64][3] = {};
-        const void* solve_fn = glob ? (const void*)ba_solve_global_kernel
-                               : opt.solve256 ? (const void*)ba_solve_kernel<256> : (const void*)ba_solve_kernel<1024>;
-        const size_t need = std::max<size_t>(ldlt_lds, 1024);
-        std::lock_guard<std::mutex> lk(mu);
-        size_t& cur = lim[device & 63][glob ? 1 : opt.solve256 ? 2 : 0];
-        if (need > cur) {
-            ORB_HIP_TRY(hipFuncSetAttribute(solve_fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)need));
-            cur = need;
-        }
-        return ORB_OK;
+        return raise_solve_lds_limit(glob ? SOLVE_HBM : opt.solve256 ? SOLVE_LDS_256 : SOLVE_LDS_1024, device, ldlt_lds);
     }
 
     // the launches of one LM trial
@@ -847,4 +854,148 @@ extern "C" int orbba_debug_ldlt_grid(const double* A, const double* b, int D, do
     *ok = okv;
     if (okv) ORB_HIP_TRY(hipMemcpy(x, g.y, (size_t)D * 8, hipMemcpyDeviceToHost));
     return ORB_OK;
+}
+
+namespace {
+
+// What both solve debug entries share: device buffers of their own (freed on every return path) and a control block
+// that lets the kernel run (done = 0) with the given lambda.
+struct SolveDebug {
+    DevBuf sys, ctl;
+    ~SolveDebug() { sys.release(); ctl.release(); }
+    int control(double lambda) {
+        if (int rc = ctl.reserve(sizeof(BACtl))) return rc;
+        BACtl c{};
+        c.lambda = lambda;
+        c.ok2 = -1;
+        ORB_HIP_TRY(hipMemcpy(ctl.ptr, &c, sizeof c, hipMemcpyHostToDevice));
+        return ORB_OK;
+    }
+    int result(const double* d_x, int D, double* x, int32_t* ok) {
+        ORB_HIP_TRY(hipGetLastError());
+        ORB_HIP_TRY(hipDeviceSynchronize());
+        BACtl c;
+        ORB_HIP_TRY(hipMemcpy(&c, ctl.ptr, sizeof c, hipMemcpyDeviceToHost));
+        ORB_HIP_TRY(hipMemcpy(x, d_x, (size_t)D * 8, hipMemcpyDeviceToHost));
+        *ok = c.ok2;
+        return ORB_OK;
+    }
+};
+
+// s_piece's sum of one entry's parts (orbba_solve.h), restated on the host in its order: part 0 + the Hpp part +
+// lambda on the diagonal, then parts 1 ..
+double s_piece_host(const double* part, double h, bool diag, double lam) {
+    double v = 0.0;
+    for (int k = 0; k < SB_SPLIT; k++) {
+        double pk = part[k];
+        if (k == 0) pk = (pk + h) + (diag ? lam : 0.0);
+        v += pk;
+    }
+    return v;
+}
+
+// the lowest `bits` mantissa bits of a finite double cleared: a and a - chop(a) add up to a without rounding
+double chop(double a, int bits) {
+    uint64_t u;
+    std::memcpy(&u, &a, 8);
+    u &= ~((1ull << bits) - 1);
+    std::memcpy(&a, &u, 8);
+    return a;
+}
+
+}  // namespace
+
+// ba_solve_kernel<1024> / <256> alone, the kernel LocalBA launches for D <= 128: A x = b for a dense symmetric A on a
+// fabricated BADev without poses or points (the pose update behind the solve does nothing).  The kernel stages S from
+// the part matrices, so A - lambda I is split here into SB_SPLIT + 1 of them that s_piece sums back to A bit for bit:
+//   * small integers in the Hpp part (diagonal 6 x 6 pose blocks only) and in parts 1 .., part 0 taking the rest,
+//     wherever that sum is exact (integer and other short-mantissa entries: every term of s_piece then matters);
+//   * else the entry's mantissa cut in three (high bits in the Hpp part on a diagonal pose block, or in part 0; middle
+//     bits in part 1; low bits in part 0), which is exact for lambda = 0;
+//   * a non-finite entry goes to part 0 as it is.
+// An entry neither split reproduces (a lambda that cannot be taken off the diagonal exactly) is an ORB_EINVAL.
+extern "C" int orbba_debug_ldlt_lds(const double* A, const double* b, int D, double lambda, int threads,
+                                    int simd0_helpers, double* x, int32_t* ok, int device) {
+    ORB_CHECK_ARG(A && b && x && ok, "null argument");
+    ORB_CHECK_ARG(D >= 2 && D <= 128 && D % 2 == 0, "D must be even, 2 .. 128");
+    ORB_CHECK_ARG(threads == 1024 || threads == 256, "threads must be 1024 or 256");
+    ORB_CHECK_ARG(simd0_helpers == 0 || simd0_helpers == 1, "simd0_helpers must be 0 or 1");
+    ORB_CHECK_ARG(std::isfinite(lambda), "lambda must be finite");
+    const size_t nA = (size_t)D * D;
+    std::vector<double> parts((SB_SPLIT + 1) * nA, 0.0);
+    for (int r = 0; r < D; r++)
+        for (int c = 0; c < D; c++) {
+            const size_t e = (size_t)r * D + c;
+            const double want = A[e];
+            const bool blk = r / 6 == c / 6, dg = r == c;
+            double p[SB_SPLIT + 1] = {};   // p[SB_SPLIT]: the Hpp part
+            auto good = [&] { return s_piece_host(p, p[SB_SPLIT], dg, lambda) == want; };
+            if (!std::isfinite(want)) {
+                p[0] = want;
+            } else {
+                const double a = dg ? want - lambda : want;
+                // integers in [-4, 4] that depend on the position and on the part, nonzero on the diagonal
+                auto noise = [&](int k) { return (double)((r * 7 + c * 13 + k * 5) % 9 - 4) + (dg ? 5.0 : 0.0); };
+                double rest = a;
+                if (blk) rest -= (p[SB_SPLIT] = noise(0));
+                for (int k = 1; k < SB_SPLIT; k++) rest -= (p[k] = noise(k));
+                p[0] = rest;
+                if (!good()) {
+                    for (int k = 0; k <= SB_SPLIT; k++) p[k] = 0.0;
+                    const double hi = chop(a, 36), mid = chop(a - hi, 18), lo = (a - hi) - mid;
+                    p[blk ? SB_SPLIT : 0] = hi;
+                    p[0] += lo;
+                    if (SB_SPLIT > 1) p[1] = mid;
+                    else p[0] += mid;
+                }
+                if (!good()) {
+                    set_error("orbba_debug_ldlt_lds: lambda cannot be taken off A's diagonal exactly");
+                    return ORB_EINVAL;
+                }
+            }
+            for (int k = 0; k <= SB_SPLIT; k++) parts[k * nA + e] = p[k];
+        }
+    ORB_HIP_TRY(hipSetDevice(device));
+    SolveDebug dbg;
+    int rc;
+    if ((rc = dbg.control(lambda)) || (rc = dbg.sys.reserve((parts.size() + 2 * (size_t)D) * 8))) return rc;
+    double* const d_parts = dbg.sys.as<double>();
+    ORB_HIP_TRY(hipMemcpy(d_parts, parts.data(), parts.size() * 8, hipMemcpyHostToDevice));
+    ORB_HIP_TRY(hipMemcpy(d_parts + parts.size(), b, (size_t)D * 8, hipMemcpyHostToDevice));
+    ORB_HIP_TRY(hipMemset(d_parts + parts.size() + D, 0xff, (size_t)D * 8));
+    BADev bd{};   // np = nl = 0: no pose is read or written
+    bd.Spart = d_parts;
+    bd.bs = d_parts + parts.size();
+    bd.x = bd.bs + D;
+    bd.ctl = dbg.ctl.as<BACtl>();
+    const size_t lds = std::max<size_t>(solve_lds_doubles(D) * 8, 16);   // LocalBACall::plan_solve's
+    if ((rc = raise_solve_lds_limit(threads == 256 ? SOLVE_LDS_256 : SOLVE_LDS_1024, device, lds))) return rc;
+    if (threads == 256) hipLaunchKernelGGL(ba_solve_kernel<256>, dim3(1), dim3(256), lds, nullptr, bd, D, simd0_helpers);
+    else hipLaunchKernelGGL(ba_solve_kernel<1024>, dim3(1), dim3(1024), lds, nullptr, bd, D, simd0_helpers);
+    return dbg.result(bd.x, D, x, ok);
+}
+
+// ba_solve_global_kernel alone, LocalBA's kernel for D > 128, which reaches ldlt_hbm_solve as OptimizeEssentialGraph's
+// eg_solve_kernel does (the padded system staged in HBM, y / dinv / vz in LDS): S = A, any D up to the pose graph's.
+extern "C" int orbba_debug_ldlt_hbm(const double* A, const double* b, int D, double* x, int32_t* ok, int device) {
+    ORB_CHECK_ARG(A && b && x && ok, "null argument");
+    ORB_CHECK_ARG(D >= 1 && D <= 7 * (ORBBA_EG_MAX_KEYFRAMES - 1), "D out of range");
+    ORB_HIP_TRY(hipSetDevice(device));
+    const size_t nA = (size_t)D * D, Dp = solve_dp(D);
+    SolveDebug dbg;
+    int rc;
+    if ((rc = dbg.control(0.0)) || (rc = dbg.sys.reserve((nA + 2 * (size_t)D + Dp * (Dp + 1)) * 8))) return rc;
+    BADev bd{};
+    bd.S = dbg.sys.as<double>();
+    bd.bs = bd.S + nA;
+    bd.x = bd.bs + D;
+    bd.Sg = bd.x + D;
+    bd.ctl = dbg.ctl.as<BACtl>();
+    ORB_HIP_TRY(hipMemcpy(bd.S, A, nA * 8, hipMemcpyHostToDevice));
+    ORB_HIP_TRY(hipMemcpy(bd.bs, b, (size_t)D * 8, hipMemcpyHostToDevice));
+    ORB_HIP_TRY(hipMemset(bd.x, 0xff, (size_t)D * 8));
+    const size_t lds = 3 * Dp * 8;   // LocalBACall::plan_solve's
+    if ((rc = raise_solve_lds_limit(SOLVE_HBM, device, lds))) return rc;
+    hipLaunchKernelGGL(ba_solve_global_kernel, dim3(1), dim3(1024), lds, nullptr, bd, D);
+    return dbg.result(bd.x, D, x, ok);
 }
