@@ -1628,6 +1628,129 @@ int orbtl_track_local_map_device(const orbtl_map* map, const orbtl_frames* frame
  * and not decreasing, log_scale_factor finite and > 0.  ORB_EINVAL otherwise. */
 int orbtl_track_local_map(const orbtl_map* map, const orbtl_frames* frames, const orbtl_result* out, int device);
 
+/* ------------------------------------------------------------------------------------------
+ * Map maintenance: the tables the other batches read, kept up to date in HBM.
+ *   orbmm_update_normal_depth   MapPoint::UpdateNormalAndDepth (src/MapPoint.cc:341-380) batched over map points:
+ *                               mp_normal and mp_max_min, the arrays orbtl_map and the Fuse / relocalisation / Sim3
+ *                               batches take, from the poses orbba_gba_update_map_device leaves.
+ *   orbmm_update_connections    KeyFrame::UpdateConnections with AddConnection / UpdateBestCovisibles
+ *                               (src/KeyFrame.cc:94-119, 235-309) batched over keyframes: the connection rows, the
+ *                               ordered rows, kf_parent, kf_first_connection and kf_covis.
+ *   orbmm_children              the GetChildren() CSR as the inverse of kf_parent.
+ *   orbmm_covis_csr             the rows packed into the CSR forms orbba_eg_tables and orbdb_query_batch take.
+ * Slots follow orbtl_map: keyframe slot k in [0, n_keyframes), map-point slot in [0, n_mappoints), -1 is null.  A
+ * slot, an offset or an index read from device memory is not trusted: one outside its table is skipped.
+ *
+ * UpdateNormalAndDepth, per point (csrc/mm_normal.h, float as the reference): a bad point, one with no observation
+ * in the table and one whose reference slot (or the keypoint index / octave read for it) is outside its table are
+ * left as they are.  Ow = (-R^T) t per keyframe, each sum ascending from 0; normal = (1. / n) * sum over the
+ * observations, in CSR order, of Normalized(Xw - Ow) (cv::norm in double, 1. / norm in double, each component narrowed
+ * after the product); dist = (float)cv::norm(Xw - Ow_ref); maxDistance = scaleFactors[octave] * dist and minDistance
+ * = maxDistance / scaleFactors[n_levels - 1], the octave that of the reference keyframe's keypoint mp_obs_idx of its
+ * observation (keypoint 0 when the reference keyframe does not observe the point: observations[referenceKF] inserts 0).
+ * Departure: the observations are summed in the caller's CSR order; the reference walks a std::map<KeyFrame*, size_t>
+ * in pointer order, which no two runs share.
+ *
+ * UpdateConnections, per batch item[0 .. n_items) of keyframe slots: the result is that of the reference's calls one
+ * after another in batch order, slots standing in for pointers.  The counter of keyframe k: for every
+ * kf_mappoint[k][i], i < kf_n[k], that is not null and not bad, +1 for every observer o with kf_id[o] != kf_id[k].
+ * An empty counter changes nothing.  A count >= ORBMM_THRESHOLD gives a pair and AddConnection(k, count) on that
+ * neighbour; with no such count the only pair is the largest count, the lowest slot among equals.  k's connection row
+ * becomes the whole counter (ascending slots), its ordered row the pairs sorted descending by (weight, slot); with
+ * kf_first_connection[k] set and kf_id[k] != 0 the parent becomes the ordered row's front and the flag clears.
+ * AddConnection on X takes effect if X has no entry for k or another weight; X's ordered row is then rebuilt from its
+ * whole connection row (UpdateBestCovisibles), entries below the threshold included.  kf_covis[X] = the first
+ * ORBDB_COVIS of the ordered row, -1 padded, rewritten with it.  A rewritten row is padded with slot -1 / weight 0 up
+ * to conn_cap.  An item outside [0, n_keyframes) is skipped.
+ * status[k] (written for every keyframe): ORBMM_OK, or ORBMM_CONN_OVERFLOW when k's connection row would at any
+ * point of the batch hold more than conn_cap entries: every array of k is then left as it came in; the other
+ * keyframes are unaffected (a keyframe's final state depends only on the events that reach it).  Capacity is checked
+ * before anything is written.  No floating point and no atomics on HBM: two runs are byte-identical.
+ *
+ * Workspace (per thread, grow-only): n_items * n_keyframes int32 counts, 20 bytes per item, 8 * n_keyframes *
+ * conn_cap bytes of working rows; 12 bytes per keyframe for orbmm_update_normal_depth.  ORBMM_WINDOW (read per
+ * call, default and at most 8192, at least 64) is the number of keyframe slots one pass of the LDS histogram covers.
+ * ---------------------------------------------------------------------------------------- */
+#define ORBMM_OK 0
+#define ORBMM_CONN_OVERFLOW 1
+#define ORBMM_THRESHOLD 15
+
+typedef struct orbmm_points {
+    int32_t n_keyframes, n_mappoints, kf_cap;
+    int32_t n_obs;                 /* entries of mp_obs_kf / mp_obs_idx (>= mp_obs_off[n_mappoints]) */
+    int32_t n_levels;              /* 1 .. 32 */
+    const float*   scale_factors;  /* host memory, n_levels: pyramid.scaleFactors */
+    const uint8_t* mp_bad;         /* [M] */
+    const float*   mp_xw;          /* [M][3] */
+    const int32_t* mp_ref_kf;      /* [M] GetReferenceKeyFrame() as a slot */
+    const int32_t* mp_obs_off;     /* [M + 1] CSR of GetObservations(): orbtl_map's */
+    const int32_t* mp_obs_kf;      /* keyframe slot of each observation */
+    const int32_t* mp_obs_idx;     /* keypoint index of each observation */
+    const float*   kf_pose;        /* [K][12] Rcw row-major, tcw (orbba_gba_map.kf_pose) */
+    const int32_t* kf_n;           /* [K] */
+    const int32_t* kf_kp_octave;   /* [K][kf_cap] keypointsUn[i].octave */
+    int32_t        n_points;       /* entries of point; ignored when point is NULL */
+    const int32_t* point;          /* optional: the point slots to update (NULL: every point) */
+    float* mp_normal;              /* [M][3] updated in place */
+    float* mp_max_min;             /* [M][2] maxDistance_, minDistance_; updated in place */
+} orbmm_points;
+
+typedef struct orbmm_graph {
+    int32_t n_keyframes, n_mappoints, kf_cap;
+    int32_t conn_cap;              /* row capacity of the four row arrays */
+    int32_t n_obs;                 /* entries of mp_obs_kf */
+    const int32_t* kf_id;          /* [K] KeyFrame::id */
+    const int32_t* kf_n;           /* [K] */
+    const int32_t* kf_mappoint;    /* [K][kf_cap] */
+    const uint8_t* mp_bad;         /* [M] */
+    const int32_t* mp_obs_off;     /* [M + 1] */
+    const int32_t* mp_obs_kf;
+    int32_t* conn_slot;            /* [K][conn_cap] connectionTo_, ascending slots */
+    int32_t* conn_weight;          /* [K][conn_cap] */
+    int32_t* n_conn;               /* [K] */
+    int32_t* ord_slot;             /* [K][conn_cap] orderedConnectedKeyFrames_ */
+    int32_t* ord_weight;           /* [K][conn_cap] orderedWeights_ */
+    int32_t* n_ord;                /* [K] */
+    uint8_t* kf_first_connection;  /* [K] firstConnection_ */
+    int32_t* kf_parent;            /* [K] */
+    int32_t* kf_covis;             /* [K][ORBDB_COVIS] */
+    int32_t* status;               /* [K] ORBMM_*; output only (orbmm_covis_csr does not read it: may be NULL there) */
+} orbmm_graph;
+
+/* The packed forms.  covis_*: orbba_eg_tables' ordered rows of every keyframe (covis_begin K + 1 entries; covis_slot
+ * and covis_weight must hold n_keyframes * conn_cap entries; a slot whose kf_bad is set, or outside the table, becomes
+ * -1).  conn_*: orbdb_query_batch's connected sets (the connection row, ascending) of the keyframes query[0 ..
+ * n_queries), conn_off n_queries + 1 entries, conn_idx n_queries * (conn_cap + 1); append_self adds the query's own
+ * slot at the end of its list.  Either group may be left out (all of its pointers NULL). */
+typedef struct orbmm_csr {
+    const uint8_t* kf_bad;         /* [K]; NULL: none is bad */
+    int32_t* covis_begin; int32_t* covis_slot; int32_t* covis_weight;
+    int32_t n_queries; const int32_t* query; int32_t append_self;
+    int32_t* conn_off; int32_t* conn_idx;
+} orbmm_csr;
+
+/* Device forms: every array in HBM but scale_factors; enqueue only on `stream`, nothing is copied back.  ORB_EINVAL
+ * for a NULL required array, negative sizes, kf_cap or conn_cap < 1, n_levels outside [1, 32] and a table of 2^31
+ * entries or more.  The workspace belongs to the calling thread: its calls must be stream-ordered. */
+int orbmm_update_normal_depth_device(const orbmm_points* p, void* stream);
+int orbmm_update_connections_device(const orbmm_graph* g, int32_t n_items, const int32_t* item, void* stream);
+/* kf_child_off (n_keyframes + 1) and kf_child_idx (n_keyframes entries), each list ascending; a parent outside
+ * [0, n_keyframes) is no parent.  One workgroup: count, scan, fill. */
+int orbmm_children_device(int32_t n_keyframes, const int32_t* kf_parent, int32_t* kf_child_off, int32_t* kf_child_idx,
+                          void* stream);
+int orbmm_covis_csr_device(const orbmm_graph* g, const orbmm_csr* out, void* stream);
+/* Host forms: every pointer is host memory, synchronous; the updated arrays are written back.  Before anything is
+ * copied, besides the checks above: both CSR offset arrays start at 0 and do not decrease and end within n_obs, every
+ * slot is in range (mp_obs_kf, item, point, query in [0, size); kf_mappoint, kf_parent, kf_covis, mp_ref_kf in
+ * [-1, size); the first n_conn / n_ord entries of a row in [0, n_keyframes)), mp_obs_idx in [0, kf_cap), kf_n in
+ * [0, kf_cap], the octaves of kf_n's keypoints in [0, n_levels), n_conn and n_ord in [0, conn_cap].  ORB_EINVAL
+ * otherwise. */
+int orbmm_update_normal_depth(const orbmm_points* p, int device);
+int orbmm_update_connections(const orbmm_graph* g, int32_t n_items, const int32_t* item, int device);
+int orbmm_children(int32_t n_keyframes, const int32_t* kf_parent, int32_t* kf_child_off, int32_t* kf_child_idx,
+                   int device);
+int orbmm_covis_csr(const orbmm_graph* g, const orbmm_csr* out, int device);
+
 const char* orb_last_error(void);
 int orb_device_count(void);
 

@@ -850,6 +850,36 @@ private:
     orbtl_map map_;
 };
 
+// Map maintenance (src/MapPoint.cc:341-380, src/KeyFrame.cc:94-119, 235-309): the host owns the arrays of orbmm_graph in
+// HBM; after the map moved on the device (orbba_gba_update_map_device, the essential graph, new points, Fuse) it enqueues
+// UpdateNormalAndDepth for the points and UpdateConnections for the keyframes on the stream the readers follow on
+// (LocalMap::TrackLocalMap, KeyFrameDatabase::DetectLoopCandidates), with nothing copied back.
+class MapMaintenance {
+public:
+    explicit MapMaintenance(const orbmm_graph& graph) : graph_(graph) {}
+
+    // MapPoint::UpdateNormalAndDepth for points.point (NULL: every point): mp_normal and mp_max_min in place
+    static void UpdateNormalAndDepth(const orbmm_points& points, void* stream = nullptr) {
+        check(orbmm_update_normal_depth_device(&points, stream), "orbmm_update_normal_depth_device");
+    }
+    // KeyFrame::UpdateConnections of the keyframe slots d_item[0 .. n_items), in order; graph.status tells overflow
+    void UpdateConnections(const int32_t* d_item, int32_t n_items, void* stream = nullptr) const {
+        check(orbmm_update_connections_device(&graph_, n_items, d_item, stream), "orbmm_update_connections_device");
+    }
+    // GetChildren() of every keyframe as the CSR orbtl_map and orbba_gba_map take
+    void UpdateChildren(int32_t* d_child_off, int32_t* d_child_idx, void* stream = nullptr) const {
+        check(orbmm_children_device(graph_.n_keyframes, graph_.kf_parent, d_child_off, d_child_idx, stream), "orbmm_children_device");
+    }
+    // the rows as orbba_eg_tables' covis_* and orbdb_query_batch's conn_*
+    void PackCovisibility(const orbmm_csr& out, void* stream = nullptr) const {
+        check(orbmm_covis_csr_device(&graph_, &out, stream), "orbmm_covis_csr_device");
+    }
+    const orbmm_graph& graph() const { return graph_; }
+
+private:
+    orbmm_graph graph_;
+};
+
 }  // namespace ORB_SLAM2_AMD
 
 #endif  // ORBSLAM2_AMD_HPP

@@ -19,6 +19,9 @@ Host mirrors of the reference's interfaces (tiantianxuabc/ORB_SLAM2_Refactored):
                                      (src/LoopClosing.cc:170-178), keyframe_db.py
   LocalMap                        <- LocalMap::Update and SearchLocalPoints' frustum pass (src/Tracking.cc:59-179,
                                      :554-642), local_map.py
+  UpdateNormalAndDepth / UpdateConnections <- MapPoint::UpdateNormalAndDepth (src/MapPoint.cc:341-380) and
+                                     KeyFrame::UpdateConnections (src/KeyFrame.cc:94-119, 235-309), with the
+                                     children and covisibility CSR exports, map_maintenance.py
 All compute runs in liborbslam2_amd.so (HIP kernels behind include/orbslam2_amd.h).
 """
 from .extractor import ORBextractor, KP_DTYPE
@@ -33,9 +36,12 @@ from .mapping import (PreparePairs, TriangulateMatches, CreateNewMapPoints, prep
                       triangulate_matches_device, create_new_map_points_device)
 from .keyframe_db import KeyFrameDatabase
 from .local_map import LocalMap
+from .map_maintenance import (UpdateNormalAndDepth, update_normal_depth_device, UpdateConnections,
+                              update_connections_device, Children, children_device, CovisCsr, covis_csr_device)
 from .synth import synth_image, shifted_pair, stereo_pair, make_pose_batch
 
-__all__ = ["KeyFrameDatabase", "LocalMap", "PreparePairs", "TriangulateMatches", "CreateNewMapPoints", "prepare_pairs_device", "triangulate_matches_device",
+__all__ = ["KeyFrameDatabase", "LocalMap", "UpdateNormalAndDepth", "update_normal_depth_device", "UpdateConnections",
+           "update_connections_device", "Children", "children_device", "CovisCsr", "covis_csr_device", "PreparePairs", "TriangulateMatches", "CreateNewMapPoints", "prepare_pairs_device", "triangulate_matches_device",
            "create_new_map_points_device", "InitializerInitialize", "initializer_initialize_device", "make_initializer_draws", "PnPsolverIterate", "pnpsolver_iterate_device", "make_pnp_draws", "Sim3SolverIterate", "sim3solver_iterate_device", "make_draws", "ORBextractor", "ORBmatcher", "ComputeStereoMatches", "Fuse", "fuse_device", "SearchByProjectionSim3",
            "search_by_projection_sim3_device", "SearchBySim3", "search_by_sim3_device", "ComputeDistinctiveDescriptors",
            "compute_distinctive_descriptors_device", "optimizer", "KP_DTYPE", "synth_image", "shifted_pair", "stereo_pair",

@@ -327,8 +327,32 @@ class OrbtlResult(C.Structure):
                                           "mp_desc", "mp_has_obs", "votes")]
 
 
-SIGNATURES = {
-    "orbx_create": (C.c_int, [C.POINTER(OrbxParams), C.c_int, C.POINTER(VP)]),
+class OrbmmPoints(C.Structure):
+    """orbmm_points (include/orbslam2_amd.h)."""
+    _fields_ = [("n_keyframes", C.c_int32), ("n_mappoints", C.c_int32), ("kf_cap", C.c_int32), ("n_obs", C.c_int32),
+                ("n_levels", C.c_int32)] + [
+        (k, C.c_void_p) for k in ("scale_factors", "mp_bad", "mp_xw", "mp_ref_kf", "mp_obs_off", "mp_obs_kf", "mp_obs_idx",
+                                  "kf_pose", "kf_n", "kf_kp_octave")] + [
+        ("n_points", C.c_int32), ("point", C.c_void_p), ("mp_normal", C.c_void_p), ("mp_max_min", C.c_void_p)]
+
+
+class OrbmmGraph(C.Structure):
+    """orbmm_graph (include/orbslam2_amd.h)."""
+    _fields_ = [("n_keyframes", C.c_int32), ("n_mappoints", C.c_int32), ("kf_cap", C.c_int32), ("conn_cap", C.c_int32),
+                ("n_obs", C.c_int32)] + [
+        (k, C.c_void_p) for k in ("kf_id", "kf_n", "kf_mappoint", "mp_bad", "mp_obs_off", "mp_obs_kf", "conn_slot",
+                                  "conn_weight", "n_conn", "ord_slot", "ord_weight", "n_ord", "kf_first_connection",
+                                  "kf_parent", "kf_covis", "status")]
+
+
+class OrbmmCsr(C.Structure):
+    """orbmm_csr (include/orbslam2_amd.h)."""
+    _fields_ = [("kf_bad", C.c_void_p), ("covis_begin", C.c_void_p), ("covis_slot", C.c_void_p),
+                ("covis_weight", C.c_void_p), ("n_queries", C.c_int32), ("query", C.c_void_p), ("append_self", C.c_int32),
+                ("conn_off", C.c_void_p), ("conn_idx", C.c_void_p)]
+
+
+SIGNATURES = {    "orbx_create": (C.c_int, [C.POINTER(OrbxParams), C.c_int, C.POINTER(VP)]),
     "orbx_destroy": (C.c_int, [VP]),
     "orbx_scale_tables": (C.c_int, [VP, VP, VP, VP, VP, VP]),
     "orbx_max_keypoints": (C.c_int, [VP, C.c_int, C.c_int, C.POINTER(I32)]),
@@ -428,6 +452,14 @@ SIGNATURES = {
     "orbdb_read_slots": (C.c_int, [VP, VP, VP]),
     "orbtl_track_local_map_device": (C.c_int, [C.POINTER(OrbtlMap), C.POINTER(OrbtlFrames), C.POINTER(OrbtlResult), VP]),
     "orbtl_track_local_map": (C.c_int, [C.POINTER(OrbtlMap), C.POINTER(OrbtlFrames), C.POINTER(OrbtlResult), C.c_int]),
+    "orbmm_update_normal_depth_device": (C.c_int, [C.POINTER(OrbmmPoints), VP]),
+    "orbmm_update_normal_depth": (C.c_int, [C.POINTER(OrbmmPoints), C.c_int]),
+    "orbmm_update_connections_device": (C.c_int, [C.POINTER(OrbmmGraph), C.c_int32, VP, VP]),
+    "orbmm_update_connections": (C.c_int, [C.POINTER(OrbmmGraph), C.c_int32, VP, C.c_int]),
+    "orbmm_children_device": (C.c_int, [C.c_int32, VP, VP, VP, VP]),
+    "orbmm_children": (C.c_int, [C.c_int32, VP, VP, VP, C.c_int]),
+    "orbmm_covis_csr_device": (C.c_int, [C.POINTER(OrbmmGraph), C.POINTER(OrbmmCsr), VP]),
+    "orbmm_covis_csr": (C.c_int, [C.POINTER(OrbmmGraph), C.POINTER(OrbmmCsr), C.c_int]),
     "orbx_pack_descriptors": (C.c_int,[VP, C.c_int, VP, VP, C.c_int, VP, C.c_int, VP]),
     "orbx_profile_enable": (C.c_int, [VP, C.c_int]),
     "orbx_profile_read": (C.c_int, [VP, VP, VP]),

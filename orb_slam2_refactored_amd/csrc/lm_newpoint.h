@@ -25,6 +25,7 @@
 #pragma once
 
 #include "init_hyp.h"
+#include "norm3.h"
 
 #define LM_HD INI_HD
 
@@ -67,8 +68,7 @@ LM_HD void lm_mul3(const float* A, const float* B, float* C) {
         for (int j = 0; j < 3; j++) C[3 * i + j] = lm_dot3(A[3 * i], A[3 * i + 1], A[3 * i + 2], B[j], B[3 + j], B[6 + j]);
 }
 
-// (float)cv::norm(v)
-LM_HD float lm_norm3(float x, float y, float z) { return (float)sqrt(((double)x * x + (double)y * y) + (double)z * z); }
+// lm_norm3, (float)cv::norm(v): norm3.h
 
 // Tcw = 12 floats (3 x 4 row-major), cam = fx, fy, cx, cy, bf, baseline
 LM_HD void lm_frame(const float* Tcw, const float* cam, LmFrame& f) {

@@ -1,0 +1,570 @@
+// orbmm.hip — map maintenance on gfx950 (include/orbslam2_amd.h, "Map maintenance"): MapPoint::UpdateNormalAndDepth
+// batched over map points, KeyFrame::UpdateConnections with AddConnection / UpdateBestCovisibles batched over
+// keyframes, the GetChildren() CSR and the packed covisibility tables.
+//
+// Reference: src/MapPoint.cc:341-380, src/KeyFrame.cc:94-119, 235-309.  The arithmetic is csrc/mm_normal.h's, the
+// sequential rules csrc/mm_connect.h's.  Passes, stream-ordered, nothing read back:
+//   mm_center_kernel   one thread per keyframe: Ow = (-R^T) t
+//   mm_normal_kernel   one thread per point: the float sum over its observations in CSR order
+//   mm_count_kernel    one workgroup per item: an LDS histogram (integer atomics) over a window of keyframe slots,
+//                      one pass per window, stored as the item's dense counter row
+//   mm_item_kernel     one wavefront per item: the largest count, its lowest and highest slot, the threshold flag
+//   mm_target_kernel   one wavefront per keyframe: the walk through the batch on a working row, the capacity check,
+//                      then the commit (two rank sorts)
+//   mm_children_kernel one workgroup: count, scan, fill with kf_parent staged in LDS tiles
+//   mm_offsets_kernel  one workgroup: the CSR offsets of the packed rows; mm_pack_kernel fills them
+#include <algorithm>
+#include <cstdlib>
+#include <vector>
+
+#include "common.h"
+#include "mm_connect.h"
+#include "mm_normal.h"
+
+namespace orbamd {
+
+constexpr int MM_WINDOW_MAX = 8192, MM_WINDOW_MIN = 64;   // int32 counters in LDS: 32 KiB at most
+constexpr int MM_TILE = 1024;
+
+struct MmWave {
+    int lane;
+    static constexpr int width = 64;
+    __device__ void sync() const { __syncthreads(); }   // one wavefront per workgroup: a wait and a fence
+    __device__ int sum(int v) const {
+#pragma unroll
+        for (int s = 32; s > 0; s >>= 1) v += __shfl_xor(v, s, 64);
+        return v;
+    }
+    __device__ int min(int v) const {
+#pragma unroll
+        for (int s = 32; s > 0; s >>= 1) v = ::min(v, __shfl_xor(v, s, 64));
+        return v;
+    }
+    __device__ int max(int v) const {
+#pragma unroll
+        for (int s = 32; s > 0; s >>= 1) v = ::max(v, __shfl_xor(v, s, 64));
+        return v;
+    }
+    __device__ int prefix(bool flag, int& total) const {
+        const unsigned long long b = __ballot(flag);
+        total = __popcll(b);
+        return __popcll(b & ((1ull << lane) - 1));
+    }
+};
+
+__global__ __launch_bounds__(256) void mm_center_kernel(const float* kf_pose, float* kf_ow, int K) {
+    const int k = blockIdx.x * 256 + threadIdx.x;
+    if (k < K) mm_center(kf_pose + 12 * (size_t)k, kf_ow + 3 * (size_t)k);
+}
+
+__global__ __launch_bounds__(256) void mm_normal_kernel(MmPoints t, const int32_t* point, int n) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    mm_update_point(t, point ? point[i] : i);
+}
+
+__global__ __launch_bounds__(256) void mm_count_kernel(MmGraph t, const int32_t* item, int32_t* cnt, int window) {
+    extern __shared__ int32_t s_hist[];
+    const int k = item[blockIdx.x], K = t.K;
+    int32_t* row = cnt + (size_t)blockIdx.x * K;
+    const bool live = k >= 0 && k < K;
+    for (int base = 0; base < K; base += window) {
+        const int w = ::min(window, K - base);
+        for (int s = threadIdx.x; s < w; s += 256) s_hist[s] = 0;
+        __syncthreads();
+        if (live)
+            for (int i = threadIdx.x; i < t.kf_cap; i += 256) {
+                const int p = mm_counted_point(t, k, i);
+                if (p < 0) continue;
+                int e0, e1;
+                mm_obs_range(t, p, e0, e1);
+                for (int e = e0; e < e1; e++) {
+                    const int o = t.mp_obs_kf[e];
+                    if (o >= base && o < base + w && mm_counted_observer(t, k, o)) atomicAdd(&s_hist[o - base], 1);
+                }
+            }
+        __syncthreads();
+        for (int s = threadIdx.x; s < w; s += 256) row[base + s] = s_hist[s];
+        __syncthreads();
+    }
+}
+
+__global__ __launch_bounds__(64) void mm_item_kernel(const int32_t* item, const int32_t* cnt, MmItem* items, int K) {
+    const MmWave g{(int)threadIdx.x};
+    const MmItem it = mm_item_summary(g, cnt + (size_t)blockIdx.x * K, K, item[blockIdx.x]);
+    if (threadIdx.x == 0) items[blockIdx.x] = it;
+}
+
+__global__ __launch_bounds__(64) void mm_target_kernel(MmGraph t, int B, const MmItem* items, const int32_t* cnt,
+                                                        int32_t* work) {
+    const MmWave g{(int)threadIdx.x};
+    const int X = blockIdx.x;
+    int32_t* ws = work + 2 * (size_t)X * t.conn_cap;
+    int32_t* ww = ws + t.conn_cap;
+    const MmWalk r = mm_walk(g, t, X, B, items, cnt, ws, ww);
+    mm_commit(g, t, X, items, ws, ww, r);
+}
+
+// Exclusive scan of count[0 .. n) by one workgroup of 256, in place allowed (every entry is read and written by one
+// thread); off[n] = the total.
+__device__ void mm_block_scan(const int32_t* count, int n, int32_t* off, int lo, int hi, int add) {
+    __shared__ int s_wave[4];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    int carry = 0;
+    for (int base = 0; base < n; base += 256) {   // uniform trip count
+        const int i = base + (int)threadIdx.x;
+        const int v = i < n ? ::min(::max(count[i], lo), hi) + add : 0;
+        int x = v;
+#pragma unroll
+        for (int d = 1; d < 64; d <<= 1) {
+            const int y = __shfl_up(x, d, 64);
+            if (lane >= d) x += y;
+        }
+        if (lane == 63) s_wave[wave] = x;
+        __syncthreads();
+        int before = 0;
+        for (int q = 0; q < wave; q++) before += s_wave[q];
+        const int total = (s_wave[0] + s_wave[1]) + (s_wave[2] + s_wave[3]);
+        if (i < n) off[i] = carry + before + x - v;
+        carry += total;
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) off[n] = carry;
+}
+
+__global__ __launch_bounds__(256) void mm_children_kernel(int K, const int32_t* parent, int32_t* off, int32_t* idx) {
+    __shared__ int32_t s_par[MM_TILE];
+    // count: off[p] = the number of k with parent[k] == p
+    for (int pb = 0; pb < K; pb += 256) {
+        const int p = pb + (int)threadIdx.x;
+        int c = 0;
+        for (int tb = 0; tb < K; tb += MM_TILE) {
+            const int w = ::min(MM_TILE, K - tb);
+            for (int j = threadIdx.x; j < w; j += 256) s_par[j] = parent[tb + j];
+            __syncthreads();
+            if (p < K)
+                for (int j = 0; j < w; j++) c += s_par[j] == p ? 1 : 0;
+            __syncthreads();
+        }
+        if (p < K) off[p] = c;
+    }
+    __syncthreads();
+    mm_block_scan(off, K, off, 0, K, 0);
+    __syncthreads();
+    // fill: k ascending per parent; the lists hold K entries at most in all
+    for (int pb = 0; pb < K; pb += 256) {
+        const int p = pb + (int)threadIdx.x;
+        int pos = p < K ? off[p] : 0;
+        for (int tb = 0; tb < K; tb += MM_TILE) {
+            const int w = ::min(MM_TILE, K - tb);
+            for (int j = threadIdx.x; j < w; j += 256) s_par[j] = parent[tb + j];
+            __syncthreads();
+            if (p < K)
+                for (int j = 0; j < w; j++)
+                    if (s_par[j] == p && pos < K) idx[pos++] = tb + j;
+            __syncthreads();
+        }
+    }
+}
+
+// mode 0: the ordered rows of every keyframe; mode 1: the connection rows of the queries (+ 1 with append_self; a
+// query outside the table has an empty list)
+__global__ __launch_bounds__(256) void mm_offsets_kernel(MmGraph t, orbmm_csr o, int mode, int32_t* q_count) {
+    if (mode == 0) {
+        mm_block_scan(t.n_ord, t.K, o.covis_begin, 0, t.conn_cap, 0);
+        return;
+    }
+    for (int q = threadIdx.x; q < o.n_queries; q += 256) {
+        const int k = o.query[q];
+        q_count[q] = (k >= 0 && k < t.K) ? mm_clamp(t.n_conn[k], 0, t.conn_cap) + (o.append_self ? 1 : 0) : 0;
+    }
+    __syncthreads();
+    mm_block_scan(q_count, o.n_queries, o.conn_off, 0, t.conn_cap + 1, 0);
+}
+
+__global__ __launch_bounds__(256) void mm_pack_kernel(MmGraph t, orbmm_csr o, int mode) {
+    const int cap = t.conn_cap, row = blockIdx.x, j = blockIdx.y * 256 + threadIdx.x;
+    if (mode == 0) {
+        if (j >= mm_clamp(t.n_ord[row], 0, cap)) return;
+        const size_t at = (size_t)o.covis_begin[row] + j;   // <= K * cap: the scan clamps as this does
+        const int s = t.ord_slot[(size_t)row * cap + j];
+        o.covis_slot[at] = (s >= 0 && s < t.K && !(o.kf_bad && o.kf_bad[s])) ? s : -1;
+        o.covis_weight[at] = t.ord_weight[(size_t)row * cap + j];
+        return;
+    }
+    const int k = o.query[row];
+    if (k < 0 || k >= t.K) return;
+    const int n = mm_clamp(t.n_conn[k], 0, cap);
+    const size_t at = (size_t)o.conn_off[row] + j;
+    if (j < n)
+        o.conn_idx[at] = t.conn_slot[(size_t)k * cap + j];
+    else if (j == n && o.append_self)
+        o.conn_idx[at] = k;
+}
+
+struct MmScratch {
+    DevBuf ws, io;
+    int device = -1;
+    void use_device(int dev) {
+        if (device != dev) {
+            ws.release();
+            io.release();
+            device = dev;
+        }
+    }
+};
+
+}  // namespace orbamd
+
+using namespace orbamd;
+
+namespace {
+
+thread_local MmScratch g_mm;
+
+constexpr long long MM_MAX_ENTRIES = 0x7fffffffLL;
+
+struct MmStage {   // bump allocation: measure, then place
+    size_t o = 0;
+    size_t take(size_t bytes) { const size_t r = o; o += align_up(std::max<size_t>(bytes, 1), 256); return r; }
+};
+
+// Host staging of one call: inputs copied in, the updated arrays copied back.
+struct MmIo {
+    struct Item { const void* host; size_t bytes; void** dev; bool in, out; size_t at; };
+    std::vector<Item> items;
+    template <class T>
+    void add(T*& field, size_t count, bool in, bool out) {
+        if (field) items.push_back({field, count * sizeof(*field), (void**)&field, in, out, 0});
+    }
+    int upload(DevBuf& buf) {
+        MmStage s;
+        for (Item& i : items) i.at = s.take(i.bytes);
+        int rc;
+        if ((rc = buf.reserve(s.o))) return rc;
+        char* d = buf.as<char>();
+        for (Item& i : items) {
+            if (i.in && i.bytes) ORB_HIP_TRY(hipMemcpy(d + i.at, i.host, i.bytes, hipMemcpyHostToDevice));
+            *i.dev = d + i.at;
+        }
+        return ORB_OK;
+    }
+    int download() {
+        for (Item& i : items)
+            if (i.out && i.bytes) ORB_HIP_TRY(hipMemcpy((void*)i.host, *i.dev, i.bytes, hipMemcpyDeviceToHost));
+        return ORB_OK;
+    }
+};
+
+int mm_check_csr(const int32_t* off, int n, int n_obs, const char* what) {
+    ORB_CHECK_ARG(off[0] == 0, std::string(what) + ": offsets must start at 0");
+    for (int i = 0; i < n; i++) ORB_CHECK_ARG(off[i + 1] >= off[i], std::string(what) + ": offsets must not decrease");
+    ORB_CHECK_ARG(off[n] <= n_obs, std::string(what) + ": offsets end past n_obs");
+    return ORB_OK;
+}
+
+int mm_check_range(const int32_t* a, size_t n, int lo, int hi, const char* msg) {
+    for (size_t i = 0; i < n; i++) ORB_CHECK_ARG(a[i] >= lo && a[i] < hi, msg);
+    return ORB_OK;
+}
+
+int mm_points_check(const orbmm_points* p) {
+    ORB_CHECK_ARG(p, "null points");
+    ORB_CHECK_ARG(p->n_keyframes >= 0 && p->n_mappoints >= 0 && p->n_obs >= 0 && (!p->point || p->n_points >= 0), "negative sizes");
+    ORB_CHECK_ARG(p->kf_cap >= 1, "kf_cap must be at least 1");
+    ORB_CHECK_ARG(p->n_levels >= 1 && p->n_levels <= MM_MAX_LEVELS, "n_levels must be in [1, 32]");
+    ORB_CHECK_ARG((long long)p->n_keyframes * p->kf_cap < MM_MAX_ENTRIES && 3LL * p->n_mappoints < MM_MAX_ENTRIES &&
+                      12LL * p->n_keyframes < MM_MAX_ENTRIES,
+                  "a table of 2^31 entries or more");
+    ORB_CHECK_ARG(p->scale_factors, "null scale_factors");
+    ORB_CHECK_ARG(p->mp_bad && p->mp_xw && p->mp_ref_kf && p->mp_obs_off && p->mp_obs_kf && p->mp_obs_idx && p->mp_normal &&
+                      p->mp_max_min,
+                  "null map-point table");
+    ORB_CHECK_ARG(p->kf_pose && p->kf_n && p->kf_kp_octave, "null keyframe table");
+    return ORB_OK;
+}
+
+int mm_points_check_host(const orbmm_points* p) {
+    const int K = p->n_keyframes, M = p->n_mappoints;
+    int rc;
+    if ((rc = mm_check_csr(p->mp_obs_off, M, p->n_obs, "mp_obs"))) return rc;
+    const size_t n_obs = p->mp_obs_off[M];
+    if ((rc = mm_check_range(p->mp_obs_kf, n_obs, 0, K, "mp_obs_kf entry outside [0, n_keyframes)"))) return rc;
+    if ((rc = mm_check_range(p->mp_obs_idx, n_obs, 0, p->kf_cap, "mp_obs_idx entry outside [0, kf_cap)"))) return rc;
+    if ((rc = mm_check_range(p->mp_ref_kf, M, -1, K, "mp_ref_kf outside [-1, n_keyframes)"))) return rc;
+    if ((rc = mm_check_range(p->kf_n, K, 0, p->kf_cap + 1, "kf_n outside [0, kf_cap]"))) return rc;
+    for (int k = 0; k < K; k++)
+        if ((rc = mm_check_range(p->kf_kp_octave + (size_t)k * p->kf_cap, p->kf_n[k], 0, p->n_levels,
+                                 "kf_kp_octave entry outside [0, n_levels)")))
+            return rc;
+    if (p->point && (rc = mm_check_range(p->point, p->n_points, 0, M, "point outside [0, n_mappoints)"))) return rc;
+    return ORB_OK;
+}
+
+int mm_graph_check(const orbmm_graph* g, bool rows_only) {
+    ORB_CHECK_ARG(g, "null graph");
+    ORB_CHECK_ARG(g->n_keyframes >= 0 && g->n_mappoints >= 0 && g->n_obs >= 0, "negative sizes");
+    ORB_CHECK_ARG(g->kf_cap >= 1 || rows_only, "kf_cap must be at least 1");
+    ORB_CHECK_ARG(g->conn_cap >= 1, "conn_cap must be at least 1");
+    ORB_CHECK_ARG((long long)g->n_keyframes * std::max(g->kf_cap, 1) < MM_MAX_ENTRIES &&
+                      (long long)g->n_keyframes * g->conn_cap < MM_MAX_ENTRIES / 2,
+                  "a table of 2^31 entries or more");
+    ORB_CHECK_ARG(g->conn_slot && g->conn_weight && g->n_conn && g->ord_slot && g->ord_weight && g->n_ord, "null row array");
+    if (rows_only) return ORB_OK;
+    ORB_CHECK_ARG(g->kf_id && g->kf_n && g->kf_mappoint && g->kf_first_connection && g->kf_parent && g->kf_covis && g->status,
+                  "null keyframe table");
+    ORB_CHECK_ARG(g->mp_bad && g->mp_obs_off && g->mp_obs_kf, "null map-point table");
+    return ORB_OK;
+}
+
+int mm_items_check(const orbmm_graph* g, int32_t n_items, const int32_t* item) {
+    ORB_CHECK_ARG(n_items >= 0, "negative sizes");
+    ORB_CHECK_ARG(n_items == 0 || item, "null item");
+    ORB_CHECK_ARG((long long)n_items * std::max(g->n_keyframes, 1) < MM_MAX_ENTRIES, "a table of 2^31 entries or more");
+    return ORB_OK;
+}
+
+int mm_rows_check_host(const orbmm_graph* g) {
+    const int K = g->n_keyframes, cap = g->conn_cap;
+    for (int k = 0; k < K; k++) {
+        ORB_CHECK_ARG(g->n_conn[k] >= 0 && g->n_conn[k] <= cap, "n_conn outside [0, conn_cap]");
+        ORB_CHECK_ARG(g->n_ord[k] >= 0 && g->n_ord[k] <= cap, "n_ord outside [0, conn_cap]");
+        int rc;
+        if ((rc = mm_check_range(g->conn_slot + (size_t)k * cap, g->n_conn[k], 0, K, "conn_slot entry outside [0, n_keyframes)"))) return rc;
+        if ((rc = mm_check_range(g->ord_slot + (size_t)k * cap, g->n_ord[k], 0, K, "ord_slot entry outside [0, n_keyframes)"))) return rc;
+    }
+    return ORB_OK;
+}
+
+int mm_graph_check_host(const orbmm_graph* g, int32_t n_items, const int32_t* item) {
+    const int K = g->n_keyframes, M = g->n_mappoints;
+    int rc;
+    if ((rc = mm_check_range(g->kf_n, K, 0, g->kf_cap + 1, "kf_n outside [0, kf_cap]"))) return rc;
+    if ((rc = mm_check_range(g->kf_mappoint, (size_t)K * g->kf_cap, -1, M, "kf_mappoint entry outside [-1, n_mappoints)"))) return rc;
+    if ((rc = mm_check_csr(g->mp_obs_off, M, g->n_obs, "mp_obs"))) return rc;
+    if ((rc = mm_check_range(g->mp_obs_kf, g->mp_obs_off[M], 0, K, "mp_obs_kf entry outside [0, n_keyframes)"))) return rc;
+    if ((rc = mm_rows_check_host(g))) return rc;
+    if ((rc = mm_check_range(g->kf_parent, K, -1, K, "kf_parent outside [-1, n_keyframes)"))) return rc;
+    if ((rc = mm_check_range(g->kf_covis, (size_t)K * MM_COVIS, -1, K, "kf_covis entry outside [-1, n_keyframes)"))) return rc;
+    return mm_check_range(item, n_items, 0, K, "item outside [0, n_keyframes)");
+}
+
+MmGraph mm_graph(const orbmm_graph& g) {
+    return MmGraph{g.n_keyframes, g.n_mappoints, g.kf_cap, g.conn_cap, g.n_obs, g.kf_id, g.kf_n, g.kf_mappoint, g.mp_bad,
+                   g.mp_obs_off, g.mp_obs_kf, g.conn_slot, g.conn_weight, g.n_conn, g.ord_slot, g.ord_weight, g.n_ord,
+                   g.kf_first_connection, g.kf_parent, g.kf_covis, g.status};
+}
+
+int mm_csr_check(const orbmm_graph* g, const orbmm_csr* o, bool& covis, bool& conn) {
+    int rc;
+    if ((rc = mm_graph_check(g, true))) return rc;
+    ORB_CHECK_ARG(o, "null csr");
+    covis = o->covis_begin || o->covis_slot || o->covis_weight;
+    conn = o->conn_off || o->conn_idx;
+    ORB_CHECK_ARG(!covis || (o->covis_begin && o->covis_slot && o->covis_weight), "null covis array");
+    ORB_CHECK_ARG(!conn || (o->conn_off && o->conn_idx), "null conn array");
+    ORB_CHECK_ARG(!conn || o->n_queries >= 0, "negative sizes");
+    ORB_CHECK_ARG(!conn || o->n_queries == 0 || o->query, "null query");
+    ORB_CHECK_ARG(!conn || (long long)o->n_queries * (g->conn_cap + 1LL) < MM_MAX_ENTRIES, "a table of 2^31 entries or more");
+    return ORB_OK;
+}
+
+int mm_window() {   // read per call
+    int w = MM_WINDOW_MAX;
+    if (const char* e = getenv("ORBMM_WINDOW")) w = atoi(e);
+    return std::max(MM_WINDOW_MIN, std::min(MM_WINDOW_MAX, w));
+}
+
+int mm_use_current_device() {
+    int dev = 0;
+    ORB_HIP_TRY(hipGetDevice(&dev));
+    g_mm.use_device(dev);
+    return ORB_OK;
+}
+
+}  // namespace
+
+extern "C" int orbmm_update_normal_depth_device(const orbmm_points* p, void* stream) {
+    int rc;
+    if ((rc = mm_points_check(p))) return rc;
+    const int n = p->point ? p->n_points : p->n_mappoints;
+    if (n == 0 || p->n_keyframes == 0) return ORB_OK;   // without keyframes no reference slot is in the table
+    if ((rc = mm_use_current_device())) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    if ((rc = g_mm.ws.reserve((size_t)p->n_keyframes * 12))) return rc;
+    MmPoints t{};
+    t.K = p->n_keyframes; t.M = p->n_mappoints; t.kf_cap = p->kf_cap; t.n_obs = p->n_obs; t.n_levels = p->n_levels;
+    t.mp_bad = p->mp_bad; t.mp_xw = p->mp_xw; t.mp_ref_kf = p->mp_ref_kf; t.mp_obs_off = p->mp_obs_off;
+    t.mp_obs_kf = p->mp_obs_kf; t.mp_obs_idx = p->mp_obs_idx; t.kf_n = p->kf_n; t.kf_kp_octave = p->kf_kp_octave;
+    t.kf_ow = g_mm.ws.as<float>(); t.mp_normal = p->mp_normal; t.mp_max_min = p->mp_max_min;
+    for (int l = 0; l < p->n_levels; l++) t.scale[l] = p->scale_factors[l];
+    hipLaunchKernelGGL(mm_center_kernel, dim3((t.K + 255) / 256), dim3(256), 0, st, p->kf_pose, g_mm.ws.as<float>(), t.K);
+    hipLaunchKernelGGL(mm_normal_kernel, dim3((n + 255) / 256), dim3(256), 0, st, t, p->point, n);
+    ORB_HIP_TRY(hipGetLastError());
+    return ORB_OK;
+}
+
+extern "C" int orbmm_update_connections_device(const orbmm_graph* g, int32_t n_items, const int32_t* item, void* stream) {
+    int rc;
+    if ((rc = mm_graph_check(g, false))) return rc;
+    if ((rc = mm_items_check(g, n_items, item))) return rc;
+    if (g->n_keyframes == 0) return ORB_OK;
+    if ((rc = mm_use_current_device())) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    const MmGraph t = mm_graph(*g);
+    const size_t K = t.K, B = n_items;
+    MmStage s;   // the counters, the item summaries, the working rows
+    const size_t o_cnt = s.take(B * K * 4), o_items = s.take(B * sizeof(MmItem)), o_work = s.take(2 * K * t.conn_cap * 4);
+    if ((rc = g_mm.ws.reserve(s.o))) return rc;
+    char* w = g_mm.ws.as<char>();
+    int32_t* cnt = (int32_t*)(w + o_cnt);
+    MmItem* items = (MmItem*)(w + o_items);
+    if (B) {
+        const int window = std::min(mm_window(), std::max((int)K, MM_WINDOW_MIN));
+        hipLaunchKernelGGL(mm_count_kernel, dim3((unsigned)B), dim3(256), (size_t)window * 4, st, t, item, cnt, window);
+        hipLaunchKernelGGL(mm_item_kernel, dim3((unsigned)B), dim3(64), 0, st, item, cnt, items, (int)K);
+    }
+    hipLaunchKernelGGL(mm_target_kernel, dim3((unsigned)K), dim3(64), 0, st, t, (int)B, items, cnt, (int32_t*)(w + o_work));
+    ORB_HIP_TRY(hipGetLastError());
+    return ORB_OK;
+}
+
+extern "C" int orbmm_children_device(int32_t n_keyframes, const int32_t* kf_parent, int32_t* kf_child_off,
+                                     int32_t* kf_child_idx, void* stream) {
+    ORB_CHECK_ARG(n_keyframes >= 0, "negative sizes");
+    ORB_CHECK_ARG(kf_child_off && (n_keyframes == 0 || (kf_parent && kf_child_idx)), "null children array");
+    hipLaunchKernelGGL(mm_children_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, n_keyframes, kf_parent, kf_child_off,
+                       kf_child_idx);
+    ORB_HIP_TRY(hipGetLastError());
+    return ORB_OK;
+}
+
+extern "C" int orbmm_covis_csr_device(const orbmm_graph* g, const orbmm_csr* out, void* stream) {
+    int rc;
+    bool covis = false, conn = false;
+    if ((rc = mm_csr_check(g, out, covis, conn))) return rc;
+    if ((rc = mm_use_current_device())) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    const MmGraph t = mm_graph(*g);
+    const unsigned cols = (unsigned)(t.conn_cap + 1 + 255) / 256;
+    if (covis) {
+        hipLaunchKernelGGL(mm_offsets_kernel, dim3(1), dim3(256), 0, st, t, *out, 0, (int32_t*)nullptr);
+        if (t.K) hipLaunchKernelGGL(mm_pack_kernel, dim3((unsigned)t.K, cols), dim3(256), 0, st, t, *out, 0);
+    }
+    if (conn) {
+        if ((rc = g_mm.io.reserve(std::max<size_t>((size_t)out->n_queries * 4, 256)))) return rc;
+        hipLaunchKernelGGL(mm_offsets_kernel, dim3(1), dim3(256), 0, st, t, *out, 1, g_mm.io.as<int32_t>());
+        if (out->n_queries) hipLaunchKernelGGL(mm_pack_kernel, dim3((unsigned)out->n_queries, cols), dim3(256), 0, st, t, *out, 1);
+    }
+    ORB_HIP_TRY(hipGetLastError());
+    return ORB_OK;
+}
+
+extern "C" int orbmm_update_normal_depth(const orbmm_points* p, int device) {
+    int rc;
+    if ((rc = mm_points_check(p))) return rc;
+    const int n = p->point ? p->n_points : p->n_mappoints;
+    if (n == 0 || p->n_keyframes == 0) return ORB_OK;
+    if ((rc = mm_points_check_host(p))) return rc;   // before any copy
+    ORB_HIP_TRY(hipSetDevice(device));
+    g_mm.use_device(device);
+    const size_t K = p->n_keyframes, M = p->n_mappoints, n_obs = p->mp_obs_off[M];
+    orbmm_points d = *p;
+    MmIo io;
+    io.add(d.mp_bad, M, true, false); io.add(d.mp_xw, M * 3, true, false); io.add(d.mp_ref_kf, M, true, false);
+    io.add(d.mp_obs_off, M + 1, true, false); io.add(d.mp_obs_kf, n_obs, true, false); io.add(d.mp_obs_idx, n_obs, true, false);
+    io.add(d.kf_pose, K * 12, true, false); io.add(d.kf_n, K, true, false); io.add(d.kf_kp_octave, K * p->kf_cap, true, false);
+    io.add(d.point, (size_t)p->n_points, true, false);
+    io.add(d.mp_normal, M * 3, true, true); io.add(d.mp_max_min, M * 2, true, true);
+    if ((rc = io.upload(g_mm.io))) return rc;
+    if ((rc = orbmm_update_normal_depth_device(&d, nullptr))) return rc;
+    ORB_HIP_TRY(hipStreamSynchronize(nullptr));
+    return io.download();
+}
+
+namespace {
+
+void mm_add_rows(MmIo& io, orbmm_graph& d, bool out) {
+    const size_t K = d.n_keyframes, rows = K * d.conn_cap;
+    io.add(d.conn_slot, rows, true, out); io.add(d.conn_weight, rows, true, out); io.add(d.n_conn, K, true, out);
+    io.add(d.ord_slot, rows, true, out); io.add(d.ord_weight, rows, true, out); io.add(d.n_ord, K, true, out);
+}
+
+}  // namespace
+
+extern "C" int orbmm_update_connections(const orbmm_graph* g, int32_t n_items, const int32_t* item, int device) {
+    int rc;
+    if ((rc = mm_graph_check(g, false))) return rc;
+    if ((rc = mm_items_check(g, n_items, item))) return rc;
+    if (g->n_keyframes == 0) return ORB_OK;
+    if ((rc = mm_graph_check_host(g, n_items, item))) return rc;   // before any copy
+    ORB_HIP_TRY(hipSetDevice(device));
+    g_mm.use_device(device);
+    const size_t K = g->n_keyframes, M = g->n_mappoints;
+    orbmm_graph d = *g;
+    const int32_t* d_item = item;
+    MmIo io;
+    io.add(d.kf_id, K, true, false); io.add(d.kf_n, K, true, false); io.add(d.kf_mappoint, K * g->kf_cap, true, false);
+    io.add(d.mp_bad, M, true, false); io.add(d.mp_obs_off, M + 1, true, false);
+    io.add(d.mp_obs_kf, (size_t)g->mp_obs_off[M], true, false);
+    mm_add_rows(io, d, true);
+    io.add(d.kf_first_connection, K, true, true); io.add(d.kf_parent, K, true, true); io.add(d.kf_covis, K * MM_COVIS, true, true);
+    io.add(d.status, K, false, true);
+    io.add(d_item, (size_t)n_items, true, false);
+    if ((rc = io.upload(g_mm.io))) return rc;
+    if ((rc = orbmm_update_connections_device(&d, n_items, d_item, nullptr))) return rc;
+    ORB_HIP_TRY(hipStreamSynchronize(nullptr));
+    return io.download();
+}
+
+extern "C" int orbmm_children(int32_t n_keyframes, const int32_t* kf_parent, int32_t* kf_child_off, int32_t* kf_child_idx,
+                              int device) {
+    ORB_CHECK_ARG(n_keyframes >= 0, "negative sizes");
+    ORB_CHECK_ARG(kf_child_off && (n_keyframes == 0 || (kf_parent && kf_child_idx)), "null children array");
+    int rc;
+    if ((rc = mm_check_range(kf_parent, n_keyframes, -1, n_keyframes, "kf_parent outside [-1, n_keyframes)"))) return rc;
+    if (n_keyframes == 0) {
+        kf_child_off[0] = 0;
+        return ORB_OK;
+    }
+    ORB_HIP_TRY(hipSetDevice(device));
+    g_mm.use_device(device);
+    const size_t K = n_keyframes;
+    MmIo io;
+    io.add(kf_parent, K, true, false); io.add(kf_child_off, K + 1, false, true); io.add(kf_child_idx, K, true, true);
+    if ((rc = io.upload(g_mm.io))) return rc;
+    if ((rc = orbmm_children_device(n_keyframes, kf_parent, kf_child_off, kf_child_idx, nullptr))) return rc;
+    ORB_HIP_TRY(hipStreamSynchronize(nullptr));
+    return io.download();
+}
+
+extern "C" int orbmm_covis_csr(const orbmm_graph* g, const orbmm_csr* out, int device) {
+    int rc;
+    bool covis = false, conn = false;
+    if ((rc = mm_csr_check(g, out, covis, conn))) return rc;
+    if ((rc = mm_rows_check_host(g))) return rc;   // before any copy
+    if (conn && (rc = mm_check_range(out->query, out->n_queries, 0, g->n_keyframes, "query outside [0, n_keyframes)"))) return rc;
+    ORB_HIP_TRY(hipSetDevice(device));
+    const size_t K = g->n_keyframes, rows = K * g->conn_cap, Q = conn ? out->n_queries : 0;
+    orbmm_graph d = *g;
+    orbmm_csr o = *out;
+    MmIo io;
+    mm_add_rows(io, d, false);
+    io.add(o.kf_bad, K, true, false);
+    if (covis) {
+        io.add(o.covis_begin, K + 1, false, true); io.add(o.covis_slot, rows, true, true);
+        io.add(o.covis_weight, rows, true, true);
+    }
+    if (conn) {
+        io.add(o.query, Q, true, false); io.add(o.conn_off, Q + 1, false, true);
+        io.add(o.conn_idx, Q * (g->conn_cap + 1), true, true);
+    }
+    // the device form's query counts live in g_mm.io: stage in a buffer of this call's own
+    DevBuf stage;
+    if ((rc = io.upload(stage))) { stage.release(); return rc; }
+    rc = orbmm_covis_csr_device(&d, &o, nullptr);
+    if (!rc && hipStreamSynchronize(nullptr) != hipSuccess) { set_error("hipStreamSynchronize failed"); rc = ORB_EHIP; }
+    if (!rc) rc = io.download();
+    stage.release();
+    return rc;
+}

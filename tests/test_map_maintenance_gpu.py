@@ -1,0 +1,205 @@
+"""Map maintenance on the GPU (orbmm_*, orb_slam2_refactored_amd/map_maintenance.py) against the restatement
+tests/map_maintenance_ref.py: every state array and both float arrays identical, floats compared as bits; a batch equals its
+items run one at a time and a rerun; the histogram window forced to three passes; an overflowing row is reported and leaves
+the others alone; the children and the packed CSRs; and the chain UpdateConnections + UpdateNormalAndDepth ->
+TrackLocalMap on one stream."""
+import numpy as np
+import pytest
+
+import local_map_cases as LC
+import local_map_ref as LR
+import map_maintenance_cases as MC
+import map_maintenance_ref as R
+from orb_slam2_refactored_amd import map_maintenance as MM
+from orb_slam2_refactored_amd import optimizer
+from orb_slam2_refactored_amd.local_map import OUT_KEYS, LocalMap
+
+pytestmark = pytest.mark.gpu
+
+COMPARED = R.STATE_KEYS + ("status",)
+
+
+def same(a, b):
+    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
+    if a.dtype == np.float32:
+        a, b = a.view(np.uint32), b.view(np.uint32)
+    return a.shape == b.shape and np.array_equal(a, b)
+
+
+def dev(d):
+    import torch
+    return {k: (torch.from_numpy(np.ascontiguousarray(v)).cuda() if isinstance(v, np.ndarray) else v) for k, v in d.items()}
+
+
+def connections_device(g, items):
+    """update_connections_device on a fresh device copy of g; the state arrays and status back as numpy."""
+    import torch
+    dg = dev(g)
+    status = MM.update_connections_device(dg, torch.tensor(list(items), dtype=torch.int32, device="cuda"))
+    torch.cuda.synchronize()
+    out = {k: dg[k].cpu().numpy() for k in R.STATE_KEYS}
+    out["status"] = status.cpu().numpy()
+    return out
+
+
+@pytest.mark.parametrize("batch", list(MC.BATCHES))
+@pytest.mark.parametrize("name", ["clean", "dirty"])
+def test_connections_equal_the_restatement(name, batch):
+    items = MC.BATCHES[batch]
+    want = MC.expected_connections(name, items)
+    got = connections_device(MC.graph(MC.case(name)), items)
+    for k in COMPARED:
+        assert same(got[k], want[k]), k
+    if name == "clean":                                  # the host form, which validates: the clean map only
+        host = MM.UpdateConnections(MC.graph(MC.case(name)), items)
+        for k in COMPARED:
+            assert same(host[k], want[k]), k
+    assert (want["status"] == 0).all() and any(not same(want[k], MC.case(name)[k]) for k in R.STATE_KEYS)
+
+
+@pytest.mark.parametrize("pts", [None, (5, 1499, 5, 10, 11, 12, 700, 33)])
+@pytest.mark.parametrize("name", ["clean", "dirty"])
+def test_normals_and_distances_equal_the_restatement(name, pts):
+    import torch
+    want_n, want_mm = MC.expected_normals(name, pts)
+    t = dev(MC.points(MC.case(name)))
+    MM.update_normal_depth_device(t, MC.SCALE, None if pts is None else torch.tensor(pts, dtype=torch.int32, device="cuda"))
+    torch.cuda.synchronize()
+    assert same(t["mp_normal"].cpu().numpy(), want_n) and same(t["mp_max_min"].cpu().numpy(), want_mm)
+    if name == "clean":
+        host_n, host_mm = MM.UpdateNormalAndDepth(MC.points(MC.case(name)), MC.SCALE, pts)
+        assert same(host_n, want_n) and same(host_mm, want_mm)
+    changed = (want_n != MC.case(name)["mp_normal"]).any(axis=1)
+    assert changed.any() and not changed[MC.case(name)["mp_bad"] != 0].any()
+
+
+def test_a_batch_equals_its_items_one_at_a_time_and_a_rerun():
+    items = MC.BATCHES["repeat"] + MC.BATCHES["five"]
+    whole = connections_device(MC.graph(MC.case("dirty")), items)
+    again = connections_device(MC.graph(MC.case("dirty")), items)
+    g = MC.graph(MC.case("dirty"))
+    for k in items:
+        one = connections_device(g, (k,))
+        assert (one["status"] == 0).all()
+        g.update({key: one[key] for key in R.STATE_KEYS})
+    for k in R.STATE_KEYS:
+        assert same(whole[k], again[k]) and same(whole[k], g[k]), k
+
+
+def test_a_small_histogram_window_takes_three_passes_with_the_same_result(monkeypatch):
+    g = MC.make_map(3, n_kf=150, kf_cap=64, n_mp=1200, conn_cap=150)      # 150 slots, 64 a pass: three passes
+    items = tuple(range(0, 150, 7)) + (149, 3)
+    want = R.update_connections({k: g[k] for k in MC.GRAPH}, list(items))
+    wide = connections_device({k: g[k] for k in MC.GRAPH}, items)
+    monkeypatch.setenv("ORBMM_WINDOW", "64")
+    narrow = connections_device({k: g[k] for k in MC.GRAPH}, items)
+    for k in COMPARED:
+        assert same(narrow[k], want[k]) and same(wide[k], want[k]), k
+    assert want["n_conn"].max() > 64                   # rows wider than one wavefront, slots in every window
+
+
+def test_a_row_one_too_narrow_reports_overflow_and_the_others_are_unchanged():
+    m = MC.make_map(0, warm=False)
+    items = (7, 23, 7)
+    full = R.update_connections(MC.graph(m), list(items))
+    widest = int(full["n_conn"].max())
+    k = int(np.argmax(full["n_conn"]))
+    assert (full["n_conn"] == widest).sum() == 1 and k == 7
+    g = MC.graph(m, conn_cap=widest - 1)
+    want = R.update_connections(g, list(items))
+    got = connections_device(g, items)
+    for key in COMPARED:
+        assert same(got[key], want[key]), key
+    assert got["status"][k] == MM.CONN_OVERFLOW and (np.delete(got["status"], k) == 0).all()
+    for key in R.STATE_KEYS:
+        assert same(got[key][k], g[key][k]), key       # the rows it came with
+        a, b = np.delete(got[key], k, axis=0), np.delete(full[key], k, axis=0)
+        assert same(a, b[:, :widest - 1] if b.ndim == 2 and b.shape[1] == MC.CONN_CAP else b), key
+
+
+def test_children_and_packed_tables_equal_the_restatement_and_feed_the_edge_list():
+    import torch
+    after = MC.expected_connections("clean", MC.BATCHES["all"])
+    g = {k: after[k] for k in R.STATE_KEYS}
+    parent = after["kf_parent"].copy()
+    parent[[2, 9]] = 30, -5                                # outside the table: no parent
+    off, idx = MM.children_device(torch.from_numpy(parent).cuda())
+    woff, widx = R.children(parent)
+    assert same(off.cpu().numpy(), woff) and same(idx.cpu().numpy()[:woff[-1]], widx) and woff[-1] > 10
+    hoff, hidx = MM.Children(after["kf_parent"])
+    assert all(same(a, b) for a, b in zip((hoff, hidx), R.children(after["kf_parent"])))
+    bad = np.zeros(MC.K, np.uint8)
+    bad[[4, 17]] = 1
+    queries = np.array([3, 0, 23, 3], np.int32)
+    want = R.covis_csr(g, bad, queries, append_self=True)
+    got = MM.covis_csr_device(dev(g), torch.from_numpy(bad).cuda(), torch.from_numpy(queries).cuda(), append_self=True)
+    host = MM.CovisCsr(g, bad, queries, append_self=True)
+    for k, n in (("covis_begin", None), ("covis_slot", want["covis_begin"][-1]), ("covis_weight", want["covis_begin"][-1]),
+                 ("conn_off", None), ("conn_idx", want["conn_off"][-1])):
+        assert same(got[k].cpu().numpy()[:n], want[k]) and same(host[k], want[k]), k
+    assert (want["covis_slot"] == -1).sum() > 5
+    plain = R.covis_csr(g, None, queries)
+    assert same(MM.CovisCsr(g, None, queries)["conn_idx"], plain["conn_idx"])
+    # essential_graph_edges on the packed tables and on host-built ones
+    K = MC.K
+    rows = lambda t: [list(zip(t["covis_slot"][b:e].tolist(), t["covis_weight"][b:e].tolist()))  # noqa: E731
+                      for b, e in zip(t["covis_begin"][:-1], t["covis_begin"][1:])]
+    tables = dict(kf_id=MC.case("clean")["kf_id"], parent=after["kf_parent"], loop_edges=[[] for _ in range(K)],
+                  loop_connections=[], curr_slot=K - 1, loop_slot=0)
+    packed = optimizer.essential_graph_edges(dict(tables, covisibles=rows({k: got[k].cpu().numpy() for k in got})), 20)
+    built = optimizer.essential_graph_edges(dict(tables, covisibles=[
+        [(-1 if bad[s] else int(s), int(w)) for s, w in zip(after["ord_slot"][k, :after["n_ord"][k]], after["ord_weight"][k, :after["n_ord"][k]])]
+        for k in range(K)]), 20)
+    assert all(same(a, b) for a, b in zip(packed, built)) and len(packed[0]) > K
+
+
+def test_the_chain_on_one_stream_feeds_the_local_map():
+    """UpdateConnections and UpdateNormalAndDepth, then TrackLocalMap reading the arrays they wrote, on one stream; the local
+    point list differs from the one stale kf_covis / mp_normal give."""
+    import torch
+    c = LC.case("mixed")
+    m, fr, _ = LC.batch(c, 3)
+    K, M, kf_cap = len(m["kf_bad"]), len(m["mp_bad"]), m["kf_mappoint"].shape[1]
+    rng = np.random.default_rng(5)
+    obs_idx = np.zeros(len(m["mp_obs_kf"]), np.int32)
+    for p in range(M):                                     # the keypoint index of each observation
+        for e in range(m["mp_obs_off"][p], m["mp_obs_off"][p + 1]):
+            hit = np.flatnonzero(m["kf_mappoint"][m["mp_obs_kf"][e]] == p)
+            obs_idx[e] = hit[0] if len(hit) else 0
+    ref_kf = np.array([m["mp_obs_kf"][m["mp_obs_off"][p]] if m["mp_obs_off"][p + 1] > m["mp_obs_off"][p] else -1 for p in range(M)], np.int32)
+    pose = np.zeros((K, 12), np.float32)
+    for k in range(K):
+        pose[k, :9] = MC.rotation(rng).reshape(-1)
+        pose[k, 9:] = rng.normal(size=3) * 3
+    scale = (1.2 ** np.arange(fr["n_levels"])).astype(np.float32)
+    extra = dict(mp_ref_kf=ref_kf, mp_obs_idx=obs_idx, kf_pose=pose, kf_kp_octave=rng.integers(0, fr["n_levels"], (K, kf_cap)).astype(np.int32),
+                 kf_id=np.arange(K, dtype=np.int32))
+    extra.update(MC.empty_state(K, K))
+    stale = dict(m, kf_covis=np.full_like(m["kf_covis"], -1), kf_parent=np.full_like(m["kf_parent"], -1))   # no graph yet
+    t = dict(stale, **extra)
+    items = list(range(K))
+    # the restatement's tables
+    conn = R.update_connections({k: t[k] for k in MC.GRAPH}, items)
+    normal, max_min = R.update_normal_depth({k: t[k] for k in MC.POINTS}, scale)
+    off, idx = R.children(conn["kf_parent"])
+    fresh = dict(m, kf_covis=conn["kf_covis"], kf_parent=conn["kf_parent"], kf_child_off=off, kf_child_idx=idx if len(idx) else np.zeros(1, np.int32),
+                 mp_normal=normal, mp_max_min=max_min)
+    fr_w = {k: (v.copy() if isinstance(v, np.ndarray) else v) for k, v in fr.items()}
+    want = LR.track_local_map({k: v.copy() for k, v in fresh.items()}, fr_w, c["mp_cap"])
+    fr_s = {k: (v.copy() if isinstance(v, np.ndarray) else v) for k, v in fr.items()}
+    old = LR.track_local_map({k: v.copy() for k, v in dict(stale, kf_child_off=np.zeros(K + 1, np.int32)).items()}, fr_s, c["mp_cap"])
+    assert not same(old["local_mp"], want["local_mp"]) or not same(old["mp_valid"], want["mp_valid"])
+    # the device chain
+    dt, dfr = dev(t), dev(fr)
+    s = torch.cuda.Stream()
+    torch.cuda.synchronize()
+    with torch.cuda.stream(s):
+        status = MM.update_connections_device(dt, torch.tensor(items, dtype=torch.int32, device="cuda"), stream=s)
+        MM.update_normal_depth_device(dt, scale, stream=s)
+        dt["kf_child_off"], dt["kf_child_idx"] = MM.children_device(dt["kf_parent"], stream=s)
+        res = LocalMap(dt).track_local_map_device(dfr, c["mp_cap"], votes=True, stream=s)
+    s.synchronize()
+    assert (status.cpu().numpy() == 0).all()
+    for k in OUT_KEYS:
+        assert same(res[k].cpu().numpy(), want[k]), k
+    assert want["n_local_mp"].min() > 0
