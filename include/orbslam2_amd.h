@@ -1751,6 +1751,122 @@ int orbmm_children(int32_t n_keyframes, const int32_t* kf_parent, int32_t* kf_ch
                    int device);
 int orbmm_covis_csr(const orbmm_graph* g, const orbmm_csr* out, int device);
 
+/* ------------------------------------------------------------------------------------------
+ * The culls of LocalMapping (src/LocalMapping.cc:335-369, 641-701), in place on the tables above, with the
+ * bookkeeping they rest on: MapPoint::SetBadFlag and EraseObservation (src/MapPoint.cc:124-182), KeyFrame::SetBadFlag
+ * and EraseConnection (src/KeyFrame.cc:379-489).  Slots as above; a slot, an offset or an index read from device
+ * memory is not trusted: one outside its table is skipped, and no store leaves a table.
+ *
+ * An erased observation stays in the CSR as mp_obs_kf = -1 (every device entry of this header skips it);
+ * orbmm_compact_observations writes the CSR without those.
+ *
+ * MapPoint::SetBadFlag(p): mp_bad[p] = 1; for every observation (o, idx) of p in range kf_mappoint[o][idx] = -1,
+ * whatever it held (EraseMapPointMatch(idx)); every observation of p is erased; mp_nobs[p] stays, as nobservations_
+ * does.
+ *
+ * orbmm_cull_map_points, per entry of recent[0 .. n_recent) (recentAddedMapPoints_), in the reference's branch order,
+ * minObservation = monocular ? 2 : 3: a bad point is dropped; (float)mp_found / (float)mp_visible < 0.25f (IEEE
+ * division: x / 0 is no reason to drop) -> SetBadFlag and dropped; cur_kf_id - mp_first_kf_id >= 2 && mp_nobs <=
+ * minObservation -> SetBadFlag and dropped; cur_kf_id - mp_first_kf_id >= 3 -> dropped; otherwise kept.  A slot
+ * outside [0, n_mappoints) is dropped.  recent is rewritten in place, its order kept; *n_recent_out = what is left.
+ * A grid kernel (the points are independent) and a one-workgroup stable compaction.
+ *
+ * orbmm_cull_keyframes: the targets are ord_slot[cur][0 .. n_ord[cur]) as they are at entry, in that order, one after
+ * another (a culled target changes what later ones see).  Target t is skipped if kf_id[t] == 0 or kf_bad[t] (the
+ * second is a departure; it cannot occur on consistent tables).  Over i1 < kf_n[t] with p = kf_mappoint[t][i1] not
+ * null and not bad: unless monocular, i1 is skipped where kf_depth[t][i1] > th_depth || kf_depth[t][i1] < 0;
+ * npoints++; if mp_nobs[p] > 3 and at least three observations (o, i2) of p have o != t and kf_kp_octave[o][i2] <=
+ * kf_kp_octave[t][i1] + 1, nredundant++.  t is culled if nredundant > 0.9 * npoints (double).  Culling t with
+ * kf_not_erase[t] set: kf_to_be_erased[t] = 1, nothing else.  Otherwise, in this order:
+ *   1. EraseConnection: every v of t's connection row loses its entry for t, if it has one; v's ordered row is then
+ *      rebuilt from its whole connection row, descending by (weight, slot), with kf_covis[v] (UpdateBestCovisibles).
+ *   2. EraseObservation: for every kf_mappoint[t][i] not null, i < kf_n[t], whose point p observes t at idx:
+ *      mp_nobs[p] -= kf_uright[t][idx] >= 0 ? 2 : 1; that observation is erased; if mp_ref_kf[p] == t it becomes the
+ *      first remaining observation in CSR order, or -1 (departure: the reference takes the first in pointer order);
+ *      if mp_nobs[p] <= 2, SetBadFlag(p).  kf_mappoint[t] itself is left, as mappoints_ is.
+ *   3. t's rows are cleared: n_conn = n_ord = 0, slot -1 / weight 0 up to conn_cap, kf_covis[t] = -1.
+ *   4. The spanning tree: the candidates start as {kf_parent[t]}; repeatedly, over the not-bad children of t in
+ *      ascending slot order (departure: pointer order) and the entries of each child's ordered row in order, an entry
+ *      whose kf_id equals a candidate's competes with its weight in the child's connection row (0 if absent); a
+ *      strictly larger weight wins, so the first met among equals stays; the winning child gets that entry as parent,
+ *      joins the candidates and leaves the children.  When no pair is found the remaining children get kf_parent[t].
+ *      kf_parent[t] stays.  kf_tcp[t] = kf_pose[t] * Inverse(kf_pose[kf_parent[t]]) in float (CameraPose.h:44-56, one
+ *      rounding per operation), left alone when the parent is outside the table.  kf_bad[t] = 1.
+ * culled[0 .. conn_cap): the culled slots in order, -1 padded: orbdb_erase_device(db, conn_cap, culled, stream) is
+ * keyFrameDB_->erase without a count crossing PCIe.  *n_culled: their number.  *status: ORBMM_OK.
+ * One launch of one workgroup of four wavefronts: all lanes over the target's row for the count and for
+ * EraseObservation, one wavefront per neighbour for EraseConnection, one for the tree, barriers between the phases.
+ * No floating-point and no HBM atomics (each point and each row has one writer per phase): two runs are
+ * byte-identical.  Tables where a point is twice in one keyframe's row (below kf_n) or a keyframe twice in one
+ * point's observations: the host entries refuse them; on the device entries the result is unspecified, but every
+ * store stays inside its table.
+ *
+ * Workspace (per thread, grow-only): n_recent bytes; 4 * (9 * conn_cap + 2 * n_keyframes + 1) bytes.
+ * ---------------------------------------------------------------------------------------- */
+typedef struct orbmm_cull {
+    int32_t n_keyframes, n_mappoints, kf_cap;
+    int32_t conn_cap;                 /* row capacity of the four row arrays; orbmm_cull_map_points ignores it */
+    int32_t n_obs;                    /* entries of mp_obs_kf / mp_obs_idx (>= mp_obs_off[n_mappoints]) */
+    /* orbmm_cull_map_points reads only the arrays marked P; the others may be NULL there */
+    const int32_t* kf_id;             /* [K] */
+    const int32_t* kf_n;              /* [K] */
+    int32_t*       kf_mappoint;       /* [K][kf_cap] P, updated */
+    const int32_t* kf_kp_octave;      /* [K][kf_cap] */
+    const float*   kf_uright;         /* [K][kf_cap] */
+    const float*   kf_depth;          /* [K][kf_cap] */
+    const float*   kf_pose;           /* [K][12] Rcw row-major, tcw */
+    uint8_t*       kf_bad;            /* [K] updated */
+    const uint8_t* kf_not_erase;      /* [K] notErase_ */
+    uint8_t*       kf_to_be_erased;   /* [K] toBeErased_, updated */
+    float*         kf_tcp;            /* [K][12] Tcp, written for the culled */
+    uint8_t*       mp_bad;            /* [M] P, updated */
+    int32_t*       mp_nobs;           /* [M] P nobservations_ (a stereo observation counts 2), updated by the keyframe cull */
+    const int32_t* mp_found;          /* [M] P */
+    const int32_t* mp_visible;        /* [M] P */
+    const int32_t* mp_first_kf_id;    /* [M] P firstKFid */
+    int32_t*       mp_ref_kf;         /* [M] updated */
+    const int32_t* mp_obs_off;        /* [M + 1] P */
+    int32_t*       mp_obs_kf;         /* P, updated: -1 where erased */
+    const int32_t* mp_obs_idx;        /* P */
+    int32_t* conn_slot; int32_t* conn_weight; int32_t* n_conn;   /* orbmm_graph's, updated */
+    int32_t* ord_slot; int32_t* ord_weight; int32_t* n_ord;
+    int32_t* kf_parent;               /* [K] updated */
+    int32_t* kf_covis;                /* [K][ORBDB_COVIS] updated */
+} orbmm_cull;
+
+/* Device forms: every array in HBM; enqueue only on `stream`, nothing is copied back.  ORB_EINVAL for a NULL required
+ * array, negative sizes, kf_cap or conn_cap < 1 and a table of 2^31 entries or more.  The workspace belongs to the
+ * calling thread: its calls must be stream-ordered. */
+int orbmm_cull_map_points_device(const orbmm_cull* c, int32_t n_recent, int32_t* recent, int32_t cur_kf_id,
+                                 int32_t monocular, int32_t* n_recent_out, void* stream);
+int orbmm_cull_keyframes_device(const orbmm_cull* c, int32_t cur, int32_t monocular, float th_depth, int32_t* culled,
+                                int32_t* n_culled, int32_t* status, void* stream);
+/* The CSR without the entries whose mp_obs_kf is -1, the order within a point kept, into out_off (n_mappoints + 1) and
+ * out_kf / out_idx (n_obs entries each, distinct from the inputs; the caller swaps the arrays).  Count per point, one
+ * scan by one workgroup, fill. */
+int orbmm_compact_observations_device(int32_t n_mappoints, int32_t n_obs, const int32_t* mp_obs_off,
+                                      const int32_t* mp_obs_kf, const int32_t* mp_obs_idx, int32_t* out_off,
+                                      int32_t* out_kf, int32_t* out_idx, void* stream);
+/* orbmm_children with the keyframes whose kf_bad is set left out as children: GetChildren() after EraseChild.
+ * (orbmm_children lists a culled keyframe under its parent, because kf_parent of a culled keyframe stays.) */
+int orbmm_children_live_device(int32_t n_keyframes, const int32_t* kf_parent, const uint8_t* kf_bad,
+                               int32_t* kf_child_off, int32_t* kf_child_idx, void* stream);
+/* Host forms: every pointer is host memory, synchronous; the updated arrays are written back.  Before anything is
+ * copied, besides the checks above: the offsets start at 0, do not decrease and end within n_obs; mp_obs_kf in
+ * [0, n_keyframes) (an erased entry is refused: compact first), mp_obs_idx in [0, kf_cap), kf_mappoint in
+ * [-1, n_mappoints), recent in [0, n_mappoints), no keyframe twice in a point's observations; for the keyframe cull
+ * also cur in [0, n_keyframes), kf_n in [0, kf_cap], mp_ref_kf and kf_parent in [-1, n_keyframes), n_conn and n_ord in
+ * [0, conn_cap], the first n_conn / n_ord entries of a row in [0, n_keyframes), no point twice in a keyframe's row.
+ * ORB_EINVAL otherwise. */
+int orbmm_cull_map_points(const orbmm_cull* c, int32_t n_recent, int32_t* recent, int32_t cur_kf_id, int32_t monocular,
+                          int32_t* n_recent_out, int device);
+int orbmm_cull_keyframes(const orbmm_cull* c, int32_t cur, int32_t monocular, float th_depth, int32_t* culled,
+                         int32_t* n_culled, int32_t* status, int device);
+int orbmm_compact_observations(int32_t n_mappoints, int32_t n_obs, const int32_t* mp_obs_off, const int32_t* mp_obs_kf,
+                               const int32_t* mp_obs_idx, int32_t* out_off, int32_t* out_kf, int32_t* out_idx, int device);
+int orbmm_children_live(int32_t n_keyframes, const int32_t* kf_parent, const uint8_t* kf_bad, int32_t* kf_child_off,
+                        int32_t* kf_child_idx, int device);
+
 const char* orb_last_error(void);
 int orb_device_count(void);
 

@@ -880,6 +880,43 @@ private:
     orbmm_graph graph_;
 };
 
+// LocalMapping's culls (src/LocalMapping.cc:335-369, 641-701): the host owns the arrays of orbmm_cull in HBM and enqueues
+// MapPointCulling before and KeyFrameCulling after the local bundle adjustment, on the stream the map-maintenance calls
+// and the readers follow on; the map never comes back to the host.  An erased observation is a -1 in mp_obs_kf until
+// CompactObservations writes the CSR without them.
+class Culling {
+public:
+    explicit Culling(const orbmm_cull& tables) : tables_(tables) {}
+
+    // MapPointCulling: d_recent (recentAddedMapPoints_ as point slots) rewritten in place, *d_n_recent_out what is left
+    void MapPointCulling(int32_t* d_recent, int32_t n_recent, int32_t cur_kf_id, bool monocular, int32_t* d_n_recent_out,
+                         void* stream = nullptr) const {
+        check(orbmm_cull_map_points_device(&tables_, n_recent, d_recent, cur_kf_id, monocular ? 1 : 0, d_n_recent_out, stream),
+              "orbmm_cull_map_points_device");
+    }
+    // KeyFrameCulling(cur): d_culled (conn_cap entries, -1 padded) is what orbdb_erase_device takes
+    void KeyFrameCulling(int32_t cur, bool monocular, float th_depth, int32_t* d_culled, int32_t* d_n_culled, int32_t* d_status,
+                         void* stream = nullptr) const {
+        check(orbmm_cull_keyframes_device(&tables_, cur, monocular ? 1 : 0, th_depth, d_culled, d_n_culled, d_status, stream),
+              "orbmm_cull_keyframes_device");
+    }
+    // the observation CSR without erased entries into arrays of the same capacity; the caller swaps them
+    void CompactObservations(int32_t* d_out_off, int32_t* d_out_kf, int32_t* d_out_idx, void* stream = nullptr) const {
+        check(orbmm_compact_observations_device(tables_.n_mappoints, tables_.n_obs, tables_.mp_obs_off, tables_.mp_obs_kf,
+                                                tables_.mp_obs_idx, d_out_off, d_out_kf, d_out_idx, stream),
+              "orbmm_compact_observations_device");
+    }
+    // GetChildren() of every keyframe with the culled left out, as the CSR orbtl_map and orbba_gba_map take
+    void UpdateLiveChildren(int32_t* d_child_off, int32_t* d_child_idx, void* stream = nullptr) const {
+        check(orbmm_children_live_device(tables_.n_keyframes, tables_.kf_parent, tables_.kf_bad, d_child_off, d_child_idx, stream),
+              "orbmm_children_live_device");
+    }
+    const orbmm_cull& tables() const { return tables_; }
+
+private:
+    orbmm_cull tables_;
+};
+
 }  // namespace ORB_SLAM2_AMD
 
 #endif  // ORBSLAM2_AMD_HPP

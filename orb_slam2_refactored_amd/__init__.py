@@ -22,6 +22,9 @@ Host mirrors of the reference's interfaces (tiantianxuabc/ORB_SLAM2_Refactored):
   UpdateNormalAndDepth / UpdateConnections <- MapPoint::UpdateNormalAndDepth (src/MapPoint.cc:341-380) and
                                      KeyFrame::UpdateConnections (src/KeyFrame.cc:94-119, 235-309), with the
                                      children and covisibility CSR exports, map_maintenance.py
+  MapPointCulling / KeyFrameCulling <- LocalMapping::MapPointCulling and KeyFrameCulling (src/LocalMapping.cc:335-369,
+                                     641-701) with MapPoint::SetBadFlag / EraseObservation and KeyFrame::SetBadFlag,
+                                     CompactObservations and LiveChildren, culling.py
 All compute runs in liborbslam2_amd.so (HIP kernels behind include/orbslam2_amd.h).
 """
 from .extractor import ORBextractor, KP_DTYPE
@@ -38,9 +41,12 @@ from .keyframe_db import KeyFrameDatabase
 from .local_map import LocalMap
 from .map_maintenance import (UpdateNormalAndDepth, update_normal_depth_device, UpdateConnections,
                               update_connections_device, Children, children_device, CovisCsr, covis_csr_device)
+from .culling import (MapPointCulling, map_point_culling_device, KeyFrameCulling, keyframe_culling_device,
+                      CompactObservations, compact_observations_device, LiveChildren, live_children_device)
 from .synth import synth_image, shifted_pair, stereo_pair, make_pose_batch
 
-__all__ = ["KeyFrameDatabase", "LocalMap", "UpdateNormalAndDepth", "update_normal_depth_device", "UpdateConnections",
+__all__ = ["MapPointCulling", "map_point_culling_device", "KeyFrameCulling", "keyframe_culling_device", "CompactObservations",
+           "compact_observations_device", "LiveChildren", "live_children_device", "KeyFrameDatabase", "LocalMap", "UpdateNormalAndDepth", "update_normal_depth_device", "UpdateConnections",
            "update_connections_device", "Children", "children_device", "CovisCsr", "covis_csr_device", "PreparePairs", "TriangulateMatches", "CreateNewMapPoints", "prepare_pairs_device", "triangulate_matches_device",
            "create_new_map_points_device", "InitializerInitialize", "initializer_initialize_device", "make_initializer_draws", "PnPsolverIterate", "pnpsolver_iterate_device", "make_pnp_draws", "Sim3SolverIterate", "sim3solver_iterate_device", "make_draws", "ORBextractor", "ORBmatcher", "ComputeStereoMatches", "Fuse", "fuse_device", "SearchByProjectionSim3",
            "search_by_projection_sim3_device", "SearchBySim3", "search_by_sim3_device", "ComputeDistinctiveDescriptors",

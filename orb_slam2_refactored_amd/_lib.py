@@ -352,6 +352,16 @@ class OrbmmCsr(C.Structure):
                 ("conn_off", C.c_void_p), ("conn_idx", C.c_void_p)]
 
 
+class OrbmmCull(C.Structure):
+    """orbmm_cull (include/orbslam2_amd.h)."""
+    _fields_ = [("n_keyframes", C.c_int32), ("n_mappoints", C.c_int32), ("kf_cap", C.c_int32), ("conn_cap", C.c_int32),
+                ("n_obs", C.c_int32)] + [
+        (k, C.c_void_p) for k in ("kf_id", "kf_n", "kf_mappoint", "kf_kp_octave", "kf_uright", "kf_depth", "kf_pose", "kf_bad",
+                                  "kf_not_erase", "kf_to_be_erased", "kf_tcp", "mp_bad", "mp_nobs", "mp_found", "mp_visible",
+                                  "mp_first_kf_id", "mp_ref_kf", "mp_obs_off", "mp_obs_kf", "mp_obs_idx", "conn_slot",
+                                  "conn_weight", "n_conn", "ord_slot", "ord_weight", "n_ord", "kf_parent", "kf_covis")]
+
+
 SIGNATURES = {    "orbx_create": (C.c_int, [C.POINTER(OrbxParams), C.c_int, C.POINTER(VP)]),
     "orbx_destroy": (C.c_int, [VP]),
     "orbx_scale_tables": (C.c_int, [VP, VP, VP, VP, VP, VP]),
@@ -460,6 +470,14 @@ SIGNATURES = {    "orbx_create": (C.c_int, [C.POINTER(OrbxParams), C.c_int, C.PO
     "orbmm_children": (C.c_int, [C.c_int32, VP, VP, VP, C.c_int]),
     "orbmm_covis_csr_device": (C.c_int, [C.POINTER(OrbmmGraph), C.POINTER(OrbmmCsr), VP]),
     "orbmm_covis_csr": (C.c_int, [C.POINTER(OrbmmGraph), C.POINTER(OrbmmCsr), C.c_int]),
+    "orbmm_cull_map_points_device": (C.c_int, [C.POINTER(OrbmmCull), C.c_int32, VP, C.c_int32, C.c_int32, VP, VP]),
+    "orbmm_cull_map_points": (C.c_int, [C.POINTER(OrbmmCull), C.c_int32, VP, C.c_int32, C.c_int32, VP, C.c_int]),
+    "orbmm_cull_keyframes_device": (C.c_int, [C.POINTER(OrbmmCull), C.c_int32, C.c_int32, C.c_float, VP, VP, VP, VP]),
+    "orbmm_cull_keyframes": (C.c_int, [C.POINTER(OrbmmCull), C.c_int32, C.c_int32, C.c_float, VP, VP, VP, C.c_int]),
+    "orbmm_compact_observations_device": (C.c_int, [C.c_int32, C.c_int32, VP, VP, VP, VP, VP, VP, VP]),
+    "orbmm_compact_observations": (C.c_int, [C.c_int32, C.c_int32, VP, VP, VP, VP, VP, VP, C.c_int]),
+    "orbmm_children_live_device": (C.c_int, [C.c_int32, VP, VP, VP, VP, VP]),
+    "orbmm_children_live": (C.c_int, [C.c_int32, VP, VP, VP, VP, C.c_int]),
     "orbx_pack_descriptors": (C.c_int,[VP, C.c_int, VP, VP, C.c_int, VP, C.c_int, VP]),
     "orbx_profile_enable": (C.c_int, [VP, C.c_int]),
     "orbx_profile_read": (C.c_int, [VP, VP, VP]),

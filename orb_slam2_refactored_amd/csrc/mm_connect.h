@@ -197,30 +197,26 @@ MM_HD MmWalk mm_walk(const G& g, const MmGraph& t, int X, int B, const MmItem* i
     return r;
 }
 
-// Writes X's rows from the walk's working row: the connection row ascending by slot, the ordered row descending by
-// (weight, slot), each entry placed at its rank (slots are distinct, so ranks are), the padding, kf_covis, the parent.
+// Writes X's rows from a working row of n entries: the connection row ascending by slot, the ordered row descending by
+// (weight, slot), each entry placed at its rank (slots are distinct, so ranks are), the padding, kf_covis and both
+// counts.  form MM_FORM_ALL orders the whole row (UpdateBestCovisibles), MM_FORM_PAIRS the pairs of `it`.
 template <class G>
-MM_HD void mm_commit(const G& g, const MmGraph& t, int X, const MmItem* items, const int32_t* ws, const int32_t* ww,
-                     const MmWalk& r) {
-    if (g.lane == 0) t.status[X] = r.status;
-    if (r.status != MM_OK || r.form == MM_FORM_NONE) return;
-    const int cap = t.conn_cap, n = r.n;
+MM_HD void mm_commit_rows(const G& g, const MmGraph& t, int X, const MmItem& it, int form, const int32_t* ws,
+                          const int32_t* ww, int n) {
+    const int cap = t.conn_cap;
     int32_t* cs = t.conn_slot + (size_t)X * cap;
     int32_t* cw = t.conn_weight + (size_t)X * cap;
     int32_t* os = t.ord_slot + (size_t)X * cap;
     int32_t* ow = t.ord_weight + (size_t)X * cap;
-    MmItem it;
-    it.kf = -1; it.any = 1; it.max_slot = -1; it.front = -1; it.max_count = 0;
-    if (r.form == MM_FORM_PAIRS) it = items[r.own];
     int n_ord = 0;
     for (int e = g.lane; e < n; e += g.width) {
         const int s = ws[e], w = ww[e];
-        const bool in = r.form == MM_FORM_ALL || mm_is_pair(it, w, s);
+        const bool in = form == MM_FORM_ALL || mm_is_pair(it, w, s);
         int below = 0, above = 0;
         for (int j = 0; j < n; j++) {
             const int sj = ws[j], wj = ww[j];
             below += sj < s ? 1 : 0;
-            if ((r.form == MM_FORM_ALL || mm_is_pair(it, wj, sj)) && mm_greater(wj, sj, w, s)) above++;
+            if ((form == MM_FORM_ALL || mm_is_pair(it, wj, sj)) && mm_greater(wj, sj, w, s)) above++;
         }
         cs[below] = s;
         cw[below] = w;
@@ -244,6 +240,20 @@ MM_HD void mm_commit(const G& g, const MmGraph& t, int X, const MmItem* items, c
     if (g.lane == 0) {
         t.n_conn[X] = n;
         t.n_ord[X] = n_ord;
+    }
+}
+
+// Writes X's rows from the walk's working row, and the parent.
+template <class G>
+MM_HD void mm_commit(const G& g, const MmGraph& t, int X, const MmItem* items, const int32_t* ws, const int32_t* ww,
+                     const MmWalk& r) {
+    if (g.lane == 0) t.status[X] = r.status;
+    if (r.status != MM_OK || r.form == MM_FORM_NONE) return;
+    MmItem it;
+    it.kf = -1; it.any = 1; it.max_slot = -1; it.front = -1; it.max_count = 0;
+    if (r.form == MM_FORM_PAIRS) it = items[r.own];
+    mm_commit_rows(g, t, X, it, r.form, ws, ww, r.n);
+    if (g.lane == 0) {
         t.parent[X] = r.parent;
         t.first[X] = r.first ? 1 : 0;
     }

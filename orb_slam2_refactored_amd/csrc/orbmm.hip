@@ -13,12 +13,19 @@
 //                      then the commit (two rank sorts)
 //   mm_children_kernel one workgroup: count, scan, fill with kf_parent staged in LDS tiles
 //   mm_offsets_kernel  one workgroup: the CSR offsets of the packed rows; mm_pack_kernel fills them
+// The culls (src/LocalMapping.cc:335-369, 641-701; the rules are csrc/mm_cull.h's):
+//   mm_cull_points_kernel     one thread per entry of the recent list: the decision and SetBadFlag;
+//   mm_cull_list_kernel       one workgroup: the stable compaction of the list in place
+//   mm_cull_keyframes_kernel  one workgroup walks the targets in order: all lanes over the target's row for the count and
+//                             for EraseObservation, one wavefront per neighbour for EraseConnection, one for the tree
+//   mm_compact_*_kernel       the observation CSR without erased entries: count per point, one scan, fill
 #include <algorithm>
 #include <cstdlib>
 #include <vector>
 
 #include "common.h"
 #include "mm_connect.h"
+#include "mm_cull.h"
 #include "mm_normal.h"
 
 namespace orbamd {
@@ -132,7 +139,9 @@ __device__ void mm_block_scan(const int32_t* count, int n, int32_t* off, int lo,
     if (threadIdx.x == 0) off[n] = carry;
 }
 
-__global__ __launch_bounds__(256) void mm_children_kernel(int K, const int32_t* parent, int32_t* off, int32_t* idx) {
+// bad (may be NULL): keyframes that are nobody's child
+__global__ __launch_bounds__(256) void mm_children_kernel(int K, const int32_t* parent, const uint8_t* bad, int32_t* off,
+                                                          int32_t* idx) {
     __shared__ int32_t s_par[MM_TILE];
     // count: off[p] = the number of k with parent[k] == p
     for (int pb = 0; pb < K; pb += 256) {
@@ -140,7 +149,7 @@ __global__ __launch_bounds__(256) void mm_children_kernel(int K, const int32_t* 
         int c = 0;
         for (int tb = 0; tb < K; tb += MM_TILE) {
             const int w = ::min(MM_TILE, K - tb);
-            for (int j = threadIdx.x; j < w; j += 256) s_par[j] = parent[tb + j];
+            for (int j = threadIdx.x; j < w; j += 256) s_par[j] = (bad && bad[tb + j]) ? -1 : parent[tb + j];
             __syncthreads();
             if (p < K)
                 for (int j = 0; j < w; j++) c += s_par[j] == p ? 1 : 0;
@@ -157,7 +166,7 @@ __global__ __launch_bounds__(256) void mm_children_kernel(int K, const int32_t* 
         int pos = p < K ? off[p] : 0;
         for (int tb = 0; tb < K; tb += MM_TILE) {
             const int w = ::min(MM_TILE, K - tb);
-            for (int j = threadIdx.x; j < w; j += 256) s_par[j] = parent[tb + j];
+            for (int j = threadIdx.x; j < w; j += 256) s_par[j] = (bad && bad[tb + j]) ? -1 : parent[tb + j];
             __syncthreads();
             if (p < K)
                 for (int j = 0; j < w; j++)
@@ -200,6 +209,108 @@ __global__ __launch_bounds__(256) void mm_pack_kernel(MmGraph t, orbmm_csr o, in
         o.conn_idx[at] = t.conn_slot[(size_t)k * cap + j];
     else if (j == n && o.append_self)
         o.conn_idx[at] = k;
+}
+
+// ---------------------------------------------------------------------------------------------- the culls
+constexpr int MM_CULL_WAVES = 4;
+
+// One wavefront of a workgroup of several: its lanes run in lockstep, so sync() only has to order its memory operations.
+struct MmSubWave : MmWave {
+    __device__ void sync() const {
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
+        __builtin_amdgcn_wave_barrier();
+    }
+};
+
+// The workgroup of MM_CULL_WAVES wavefronts; s: MM_CULL_WAVES ints of LDS.
+struct MmBlock {
+    int lane;
+    int32_t* s;
+    static constexpr int width = 64 * MM_CULL_WAVES;
+    __device__ void sync() const { __syncthreads(); }
+    template <class Op>
+    __device__ int across(int v, Op op) const {   // v: this wavefront's value
+        if ((lane & 63) == 0) s[lane >> 6] = v;
+        __syncthreads();
+        int r = s[0];
+#pragma unroll
+        for (int q = 1; q < MM_CULL_WAVES; q++) r = op(r, s[q]);
+        __syncthreads();
+        return r;
+    }
+    __device__ int sum(int v) const { return across(MmWave{lane & 63}.sum(v), [](int a, int b) { return a + b; }); }
+    __device__ int min(int v) const { return across(MmWave{lane & 63}.min(v), [](int a, int b) { return ::min(a, b); }); }
+    __device__ int max(int v) const { return across(MmWave{lane & 63}.max(v), [](int a, int b) { return ::max(a, b); }); }
+    __device__ int prefix(bool flag, int& total) const {
+        int mine;
+        const int off = MmWave{lane & 63}.prefix(flag, mine);
+        if ((lane & 63) == 0) s[lane >> 6] = mine;
+        __syncthreads();
+        int before = 0;
+        total = 0;
+#pragma unroll
+        for (int q = 0; q < MM_CULL_WAVES; q++) {
+            before += q < (lane >> 6) ? s[q] : 0;
+            total += s[q];
+        }
+        __syncthreads();
+        return before + off;
+    }
+};
+
+__global__ __launch_bounds__(256) void mm_cull_points_kernel(MmCull t, const int32_t* recent, int n, int cur_kf_id, int min_obs,
+                                                             uint8_t* keep) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const int p = recent[i], d = cull_point_decision(t, p, cur_kf_id, min_obs);
+    if (d == CULL_BAD) cull_set_bad(t, p);
+    keep[i] = d == CULL_KEEP ? 1 : 0;
+}
+
+// recent[0 .. n) without the entries whose keep is 0, in place: a chunk is read before anything of it is written, and
+// what is written lies at or below it.
+__global__ __launch_bounds__(64 * MM_CULL_WAVES) void mm_cull_list_kernel(int32_t* recent, int n, const uint8_t* keep,
+                                                                           int32_t* n_out) {
+    __shared__ int32_t s_red[MM_CULL_WAVES];
+    const MmBlock b{(int)threadIdx.x, s_red};
+    int at = 0;
+    for (int base = 0; base < n; base += b.width) {   // uniform trip count
+        const int i = base + b.lane;
+        const bool flag = i < n && keep[i];
+        const int v = i < n ? recent[i] : -1;
+        int total;
+        const int off = b.prefix(flag, total);   // syncs: every lane has read its entry
+        if (flag) recent[at + off] = v;
+        at += total;
+    }
+    if (b.lane == 0) *n_out = at;
+}
+
+__global__ __launch_bounds__(64 * MM_CULL_WAVES) void mm_cull_keyframes_kernel(MmCull t, int cur, int monocular, float th_depth,
+                                                                                int32_t* culled, int32_t* n_culled,
+                                                                                int32_t* status, int32_t* scratch) {
+    __shared__ int32_t s_red[MM_CULL_WAVES];
+    const MmBlock b{(int)threadIdx.x, s_red};
+    MmSubWave w;
+    w.lane = (int)threadIdx.x & 63;
+    cull_keyframes(b, w, (int)threadIdx.x >> 6, MM_CULL_WAVES, t, cur, monocular != 0, th_depth, culled, n_culled, status, scratch);
+}
+
+__global__ __launch_bounds__(256) void mm_compact_count_kernel(int M, int n_obs, const int32_t* off, const int32_t* kf,
+                                                               int32_t* out_off) {
+    const int p = blockIdx.x * 256 + threadIdx.x;
+    if (p < M) out_off[p] = cull_compact_point(n_obs, off, kf, nullptr, p, 0, nullptr, nullptr);
+}
+
+__global__ __launch_bounds__(256) void mm_compact_scan_kernel(int M, int n_obs, int32_t* out_off) {
+    mm_block_scan(out_off, M, out_off, 0, n_obs, 0);
+}
+
+__global__ __launch_bounds__(256) void mm_compact_fill_kernel(int M, int n_obs, const int32_t* off, const int32_t* kf,
+                                                              const int32_t* idx, const int32_t* out_off, int32_t* out_kf,
+                                                              int32_t* out_idx) {
+    const int p = blockIdx.x * 256 + threadIdx.x;
+    if (p < M) cull_compact_point(n_obs, off, kf, idx, p, out_off[p], out_kf, out_idx);
 }
 
 struct MmScratch {
@@ -433,8 +544,8 @@ extern "C" int orbmm_children_device(int32_t n_keyframes, const int32_t* kf_pare
                                      int32_t* kf_child_idx, void* stream) {
     ORB_CHECK_ARG(n_keyframes >= 0, "negative sizes");
     ORB_CHECK_ARG(kf_child_off && (n_keyframes == 0 || (kf_parent && kf_child_idx)), "null children array");
-    hipLaunchKernelGGL(mm_children_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, n_keyframes, kf_parent, kf_child_off,
-                       kf_child_idx);
+    hipLaunchKernelGGL(mm_children_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, n_keyframes, kf_parent,
+                       (const uint8_t*)nullptr, kf_child_off, kf_child_idx);
     ORB_HIP_TRY(hipGetLastError());
     return ORB_OK;
 }
@@ -567,4 +678,243 @@ extern "C" int orbmm_covis_csr(const orbmm_graph* g, const orbmm_csr* out, int d
     if (!rc) rc = io.download();
     stage.release();
     return rc;
+}
+
+// ---------------------------------------------------------------------------------------------- the culls: entries
+namespace {
+
+MmCull mm_cull(const orbmm_cull& c) {
+    return MmCull{c.n_keyframes, c.n_mappoints, c.kf_cap, c.conn_cap, c.n_obs, c.kf_id, c.kf_n, c.kf_mappoint, c.kf_kp_octave,
+                  c.kf_uright, c.kf_depth, c.kf_pose, c.kf_bad, c.kf_not_erase, c.kf_to_be_erased, c.kf_tcp, c.mp_bad, c.mp_nobs,
+                  c.mp_found, c.mp_visible, c.mp_first_kf_id, c.mp_ref_kf, c.mp_obs_off, c.mp_obs_kf, c.mp_obs_idx, c.conn_slot,
+                  c.conn_weight, c.n_conn, c.ord_slot, c.ord_weight, c.n_ord, c.kf_parent, c.kf_covis};
+}
+
+int mm_cull_check(const orbmm_cull* c, bool keyframes) {
+    ORB_CHECK_ARG(c, "null cull tables");
+    ORB_CHECK_ARG(c->n_keyframes >= 0 && c->n_mappoints >= 0 && c->n_obs >= 0, "negative sizes");
+    ORB_CHECK_ARG(c->kf_cap >= 1, "kf_cap must be at least 1");
+    ORB_CHECK_ARG(!keyframes || c->conn_cap >= 1, "conn_cap must be at least 1");
+    ORB_CHECK_ARG((long long)c->n_keyframes * c->kf_cap < MM_MAX_ENTRIES && 12LL * c->n_keyframes < MM_MAX_ENTRIES &&
+                      (!keyframes || (long long)c->n_keyframes * c->conn_cap < MM_MAX_ENTRIES / 2),
+                  "a table of 2^31 entries or more");
+    ORB_CHECK_ARG(c->kf_mappoint && c->mp_bad && c->mp_nobs && c->mp_obs_off && c->mp_obs_kf && c->mp_obs_idx, "null map-point table");
+    if (!keyframes) {
+        ORB_CHECK_ARG(c->mp_found && c->mp_visible && c->mp_first_kf_id, "null map-point table");
+        return ORB_OK;
+    }
+    ORB_CHECK_ARG(c->mp_ref_kf, "null map-point table");
+    ORB_CHECK_ARG(c->kf_id && c->kf_n && c->kf_kp_octave && c->kf_uright && c->kf_depth && c->kf_pose && c->kf_bad &&
+                      c->kf_not_erase && c->kf_to_be_erased && c->kf_tcp && c->kf_parent && c->kf_covis,
+                  "null keyframe table");
+    ORB_CHECK_ARG(c->conn_slot && c->conn_weight && c->n_conn && c->ord_slot && c->ord_weight && c->n_ord, "null row array");
+    return ORB_OK;
+}
+
+// The host entries' checks of the tables both culls read.
+int mm_cull_check_host(const orbmm_cull* c, bool keyframes) {
+    const int K = c->n_keyframes, M = c->n_mappoints;
+    int rc;
+    if ((rc = mm_check_csr(c->mp_obs_off, M, c->n_obs, "mp_obs"))) return rc;
+    const size_t n_obs = c->mp_obs_off[M];
+    if ((rc = mm_check_range(c->mp_obs_kf, n_obs, 0, K, "mp_obs_kf entry outside [0, n_keyframes)"))) return rc;
+    if ((rc = mm_check_range(c->mp_obs_idx, n_obs, 0, c->kf_cap, "mp_obs_idx entry outside [0, kf_cap)"))) return rc;
+    if ((rc = mm_check_range(c->kf_mappoint, (size_t)K * c->kf_cap, -1, M, "kf_mappoint entry outside [-1, n_mappoints)"))) return rc;
+    std::vector<int32_t> seen(K, -1);   // a keyframe twice in a point's observations
+    for (int p = 0; p < M; p++)
+        for (int e = c->mp_obs_off[p]; e < c->mp_obs_off[p + 1]; e++) {
+            ORB_CHECK_ARG(seen[c->mp_obs_kf[e]] != p, "a keyframe twice in a map point's observations");
+            seen[c->mp_obs_kf[e]] = p;
+        }
+    if (!keyframes) return ORB_OK;
+    if ((rc = mm_check_range(c->kf_n, K, 0, c->kf_cap + 1, "kf_n outside [0, kf_cap]"))) return rc;
+    seen.assign(M, -1);                 // a point twice in a keyframe's row
+    for (int k = 0; k < K; k++)
+        for (int i = 0; i < c->kf_n[k]; i++) {
+            const int p = c->kf_mappoint[(size_t)k * c->kf_cap + i];
+            if (p < 0) continue;
+            ORB_CHECK_ARG(seen[p] != k, "a map point twice in a keyframe's row");
+            seen[p] = k;
+        }
+    if ((rc = mm_check_range(c->mp_ref_kf, M, -1, K, "mp_ref_kf outside [-1, n_keyframes)"))) return rc;
+    if ((rc = mm_check_range(c->kf_parent, K, -1, K, "kf_parent outside [-1, n_keyframes)"))) return rc;
+    for (int k = 0; k < K; k++) {
+        ORB_CHECK_ARG(c->n_conn[k] >= 0 && c->n_conn[k] <= c->conn_cap, "n_conn outside [0, conn_cap]");
+        ORB_CHECK_ARG(c->n_ord[k] >= 0 && c->n_ord[k] <= c->conn_cap, "n_ord outside [0, conn_cap]");
+        if ((rc = mm_check_range(c->conn_slot + (size_t)k * c->conn_cap, c->n_conn[k], 0, K, "conn_slot entry outside [0, n_keyframes)"))) return rc;
+        if ((rc = mm_check_range(c->ord_slot + (size_t)k * c->conn_cap, c->n_ord[k], 0, K, "ord_slot entry outside [0, n_keyframes)"))) return rc;
+    }
+    return ORB_OK;
+}
+
+void mm_cull_add(MmIo& io, orbmm_cull& d, bool keyframes) {
+    const size_t K = d.n_keyframes, M = d.n_mappoints, n_obs = d.mp_obs_off[M], rows = K * (keyframes ? d.conn_cap : 0);
+    io.add(d.kf_mappoint, K * d.kf_cap, true, true); io.add(d.mp_bad, M, true, true); io.add(d.mp_nobs, M, true, keyframes);
+    io.add(d.mp_obs_kf, n_obs, true, true); io.add(d.mp_obs_idx, n_obs, true, false);
+    if (!keyframes) {
+        io.add(d.mp_found, M, true, false); io.add(d.mp_visible, M, true, false); io.add(d.mp_first_kf_id, M, true, false);
+        io.add(d.mp_obs_off, M + 1, true, false);
+        return;
+    }
+    io.add(d.mp_ref_kf, M, true, true);
+    io.add(d.kf_id, K, true, false); io.add(d.kf_n, K, true, false); io.add(d.kf_kp_octave, K * d.kf_cap, true, false);
+    io.add(d.kf_uright, K * d.kf_cap, true, false); io.add(d.kf_depth, K * d.kf_cap, true, false);
+    io.add(d.kf_pose, K * 12, true, false); io.add(d.kf_bad, K, true, true); io.add(d.kf_not_erase, K, true, false);
+    io.add(d.kf_to_be_erased, K, true, true); io.add(d.kf_tcp, K * 12, true, true);
+    io.add(d.conn_slot, rows, true, true); io.add(d.conn_weight, rows, true, true); io.add(d.n_conn, K, true, true);
+    io.add(d.ord_slot, rows, true, true); io.add(d.ord_weight, rows, true, true); io.add(d.n_ord, K, true, true);
+    io.add(d.kf_parent, K, true, true); io.add(d.kf_covis, K * MM_COVIS, true, true);
+    io.add(d.mp_obs_off, M + 1, true, false);
+}
+
+}  // namespace
+
+extern "C" int orbmm_cull_map_points_device(const orbmm_cull* c, int32_t n_recent, int32_t* recent, int32_t cur_kf_id,
+                                            int32_t monocular, int32_t* n_recent_out, void* stream) {
+    int rc;
+    if ((rc = mm_cull_check(c, false))) return rc;
+    ORB_CHECK_ARG(n_recent >= 0, "negative sizes");
+    ORB_CHECK_ARG(n_recent_out && (n_recent == 0 || recent), "null recent list");
+    if ((rc = mm_use_current_device())) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    if ((rc = g_mm.ws.reserve(std::max<size_t>(n_recent, 256)))) return rc;
+    uint8_t* keep = g_mm.ws.as<uint8_t>();
+    if (n_recent)
+        hipLaunchKernelGGL(mm_cull_points_kernel, dim3((n_recent + 255) / 256), dim3(256), 0, st, mm_cull(*c), recent, n_recent,
+                           cur_kf_id, monocular ? 2 : 3, keep);
+    hipLaunchKernelGGL(mm_cull_list_kernel, dim3(1), dim3(64 * MM_CULL_WAVES), 0, st, recent, n_recent, keep, n_recent_out);
+    ORB_HIP_TRY(hipGetLastError());
+    return ORB_OK;
+}
+
+extern "C" int orbmm_cull_keyframes_device(const orbmm_cull* c, int32_t cur, int32_t monocular, float th_depth, int32_t* culled,
+                                           int32_t* n_culled, int32_t* status, void* stream) {
+    int rc;
+    if ((rc = mm_cull_check(c, true))) return rc;
+    ORB_CHECK_ARG(culled && n_culled && status, "null output");
+    if ((rc = mm_use_current_device())) return rc;
+    if ((rc = g_mm.ws.reserve(4 * cull_scratch_entries(c->n_keyframes, c->conn_cap, MM_CULL_WAVES)))) return rc;
+    hipLaunchKernelGGL(mm_cull_keyframes_kernel, dim3(1), dim3(64 * MM_CULL_WAVES), 0, (hipStream_t)stream, mm_cull(*c), cur,
+                       monocular, th_depth, culled, n_culled, status, g_mm.ws.as<int32_t>());
+    ORB_HIP_TRY(hipGetLastError());
+    return ORB_OK;
+}
+
+namespace {
+
+int mm_compact_check(int32_t M, int32_t n_obs, const int32_t* off, const int32_t* kf, const int32_t* idx, int32_t* out_off,
+                     int32_t* out_kf, int32_t* out_idx) {
+    ORB_CHECK_ARG(M >= 0 && n_obs >= 0, "negative sizes");
+    ORB_CHECK_ARG(off && out_off && (n_obs == 0 || (kf && idx && out_kf && out_idx)), "null observation array");
+    return ORB_OK;
+}
+
+}  // namespace
+
+extern "C" int orbmm_compact_observations_device(int32_t n_mappoints, int32_t n_obs, const int32_t* mp_obs_off,
+                                                 const int32_t* mp_obs_kf, const int32_t* mp_obs_idx, int32_t* out_off,
+                                                 int32_t* out_kf, int32_t* out_idx, void* stream) {
+    int rc;
+    if ((rc = mm_compact_check(n_mappoints, n_obs, mp_obs_off, mp_obs_kf, mp_obs_idx, out_off, out_kf, out_idx))) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    const int M = n_mappoints;
+    const dim3 grid((M + 255) / 256);
+    if (M) hipLaunchKernelGGL(mm_compact_count_kernel, grid, dim3(256), 0, st, M, n_obs, mp_obs_off, mp_obs_kf, out_off);
+    hipLaunchKernelGGL(mm_compact_scan_kernel, dim3(1), dim3(256), 0, st, M, n_obs, out_off);
+    if (M)
+        hipLaunchKernelGGL(mm_compact_fill_kernel, grid, dim3(256), 0, st, M, n_obs, mp_obs_off, mp_obs_kf, mp_obs_idx, out_off,
+                           out_kf, out_idx);
+    ORB_HIP_TRY(hipGetLastError());
+    return ORB_OK;
+}
+
+extern "C" int orbmm_children_live_device(int32_t n_keyframes, const int32_t* kf_parent, const uint8_t* kf_bad,
+                                          int32_t* kf_child_off, int32_t* kf_child_idx, void* stream) {
+    ORB_CHECK_ARG(n_keyframes >= 0, "negative sizes");
+    ORB_CHECK_ARG(kf_child_off && (n_keyframes == 0 || (kf_parent && kf_bad && kf_child_idx)), "null children array");
+    hipLaunchKernelGGL(mm_children_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, n_keyframes, kf_parent, kf_bad,
+                       kf_child_off, kf_child_idx);
+    ORB_HIP_TRY(hipGetLastError());
+    return ORB_OK;
+}
+
+extern "C" int orbmm_cull_map_points(const orbmm_cull* c, int32_t n_recent, int32_t* recent, int32_t cur_kf_id,
+                                     int32_t monocular, int32_t* n_recent_out, int device) {
+    int rc;
+    if ((rc = mm_cull_check(c, false))) return rc;
+    ORB_CHECK_ARG(n_recent >= 0, "negative sizes");
+    ORB_CHECK_ARG(n_recent_out && (n_recent == 0 || recent), "null recent list");
+    if ((rc = mm_cull_check_host(c, false))) return rc;   // before any copy
+    if ((rc = mm_check_range(recent, n_recent, 0, c->n_mappoints, "recent entry outside [0, n_mappoints)"))) return rc;
+    ORB_HIP_TRY(hipSetDevice(device));
+    g_mm.use_device(device);
+    orbmm_cull d = *c;
+    MmIo io;
+    mm_cull_add(io, d, false);
+    io.add(recent, (size_t)n_recent, true, true); io.add(n_recent_out, 1, false, true);
+    if ((rc = io.upload(g_mm.io))) return rc;
+    if ((rc = orbmm_cull_map_points_device(&d, n_recent, recent, cur_kf_id, monocular, n_recent_out, nullptr))) return rc;
+    ORB_HIP_TRY(hipStreamSynchronize(nullptr));
+    return io.download();
+}
+
+extern "C" int orbmm_cull_keyframes(const orbmm_cull* c, int32_t cur, int32_t monocular, float th_depth, int32_t* culled,
+                                    int32_t* n_culled, int32_t* status, int device) {
+    int rc;
+    if ((rc = mm_cull_check(c, true))) return rc;
+    ORB_CHECK_ARG(culled && n_culled && status, "null output");
+    if ((rc = mm_cull_check_host(c, true))) return rc;   // before any copy
+    ORB_CHECK_ARG(cur >= 0 && cur < c->n_keyframes, "cur outside [0, n_keyframes)");
+    ORB_HIP_TRY(hipSetDevice(device));
+    g_mm.use_device(device);
+    orbmm_cull d = *c;
+    MmIo io;
+    mm_cull_add(io, d, true);
+    io.add(culled, (size_t)c->conn_cap, false, true); io.add(n_culled, 1, false, true); io.add(status, 1, false, true);
+    if ((rc = io.upload(g_mm.io))) return rc;
+    if ((rc = orbmm_cull_keyframes_device(&d, cur, monocular, th_depth, culled, n_culled, status, nullptr))) return rc;
+    ORB_HIP_TRY(hipStreamSynchronize(nullptr));
+    return io.download();
+}
+
+extern "C" int orbmm_compact_observations(int32_t n_mappoints, int32_t n_obs, const int32_t* mp_obs_off, const int32_t* mp_obs_kf,
+                                          const int32_t* mp_obs_idx, int32_t* out_off, int32_t* out_kf, int32_t* out_idx,
+                                          int device) {
+    int rc;
+    if ((rc = mm_compact_check(n_mappoints, n_obs, mp_obs_off, mp_obs_kf, mp_obs_idx, out_off, out_kf, out_idx))) return rc;
+    if ((rc = mm_check_csr(mp_obs_off, n_mappoints, n_obs, "mp_obs"))) return rc;   // before any copy
+    ORB_HIP_TRY(hipSetDevice(device));
+    g_mm.use_device(device);
+    const size_t M = n_mappoints, n = n_obs;
+    MmIo io;
+    io.add(mp_obs_off, M + 1, true, false); io.add(mp_obs_kf, n, true, false); io.add(mp_obs_idx, n, true, false);
+    io.add(out_off, M + 1, false, true); io.add(out_kf, n, true, true); io.add(out_idx, n, true, true);
+    if ((rc = io.upload(g_mm.io))) return rc;
+    if ((rc = orbmm_compact_observations_device(n_mappoints, n_obs, mp_obs_off, mp_obs_kf, mp_obs_idx, out_off, out_kf, out_idx,
+                                                nullptr)))
+        return rc;
+    ORB_HIP_TRY(hipStreamSynchronize(nullptr));
+    return io.download();
+}
+
+extern "C" int orbmm_children_live(int32_t n_keyframes, const int32_t* kf_parent, const uint8_t* kf_bad, int32_t* kf_child_off,
+                                   int32_t* kf_child_idx, int device) {
+    ORB_CHECK_ARG(n_keyframes >= 0, "negative sizes");
+    ORB_CHECK_ARG(kf_child_off && (n_keyframes == 0 || (kf_parent && kf_bad && kf_child_idx)), "null children array");
+    int rc;
+    if ((rc = mm_check_range(kf_parent, n_keyframes, -1, n_keyframes, "kf_parent outside [-1, n_keyframes)"))) return rc;
+    if (n_keyframes == 0) {
+        kf_child_off[0] = 0;
+        return ORB_OK;
+    }
+    ORB_HIP_TRY(hipSetDevice(device));
+    g_mm.use_device(device);
+    const size_t K = n_keyframes;
+    MmIo io;
+    io.add(kf_parent, K, true, false); io.add(kf_bad, K, true, false); io.add(kf_child_off, K + 1, false, true);
+    io.add(kf_child_idx, K, true, true);
+    if ((rc = io.upload(g_mm.io))) return rc;
+    if ((rc = orbmm_children_live_device(n_keyframes, kf_parent, kf_bad, kf_child_off, kf_child_idx, nullptr))) return rc;
+    ORB_HIP_TRY(hipStreamSynchronize(nullptr));
+    return io.download();
 }
