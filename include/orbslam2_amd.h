@@ -1867,6 +1867,143 @@ int orbmm_compact_observations(int32_t n_mappoints, int32_t n_obs, const int32_t
 int orbmm_children_live(int32_t n_keyframes, const int32_t* kf_parent, const uint8_t* kf_bad, int32_t* kf_child_off,
                         int32_t* kf_child_idx, int device);
 
+/* ------------------------------------------------------------------------------------------
+ * Observation edits: the insert half of the observation graph, in place on the tables above.  MapPoint::AddObservation
+ * and MapPoint::Replace (src/MapPoint.cc:109-122, 191-230) and the three loops that use them: ProcessNewKeyFrame's
+ * (src/LocalMapping.cc:309-326), Fuse's apply loops (src/ORBmatcher.cc:957-976; :1070-1084 with
+ * src/LoopClosing.cc:652-657) and CorrectLoop's matched points (src/LoopClosing.cc:617-634).  Slots as above; a slot, an
+ * offset or an index read from device memory is not trusted: one outside its table is skipped, and no store leaves a
+ * table.
+ *
+ * Row slack.  A point's row is [mp_obs_off[p], mp_obs_off[p + 1]); an entry whose mp_obs_kf is outside [0, K) is free
+ * (-1 is what the culls leave).  mp_obs_off is never rewritten by an edit; orbmm_grow_observations makes room.
+ *
+ * AddObservation(p, k, idx): nothing if k is a live entry of p's row.  Otherwise the new entry goes before the first
+ * live entry whose keyframe slot is greater than k (last if there is none), the row's live entries are packed to its
+ * front in that order, the rest of the row is -1 in mp_obs_kf and mp_obs_idx, and mp_nobs[p] += kf_uright[k][idx] >= 0
+ * ? 2 : 1.  Departure: the rows are kept ascending in keyframe slot, which stands in for the pointer order of
+ * std::map<KeyFrame*, size_t>, as slot order does for the children and the votes elsewhere.  A row without a free
+ * entry: nothing is written and the step reports ORBMM_OBS_OVERFLOW.
+ *
+ * Replace(loser -> survivor): nothing if they are one slot (the id test).  The survivor's bad flag is not tested.  Per
+ * live entry (o, idx) of the loser: if the survivor does not observe o, kf_mappoint[o][idx] = survivor and
+ * AddObservation(survivor, o, idx); otherwise kf_mappoint[o][idx] = -1.  Then mp_found and mp_visible of the loser are
+ * added to the survivor's, the loser's row is all -1 (mp_obs_idx stays), mp_bad[loser] = 1, mp_replaced[loser] =
+ * survivor; mp_nobs[loser] stays.  A survivor that gains nothing keeps its row as it is.  On ascending rows the new
+ * row is the sorted union of the two, and it is built that way: every entry is placed at its rank.  If the union
+ * does not fit the survivor's row, nothing of this Replace is written: ORBMM_OBS_OVERFLOW.
+ * Departure: the reference recomputes the survivor's descriptor inside each Replace; here the caller recomputes once,
+ * after the walk, on the final observations (the `touched` list).  The two differ only where a survivor gains a
+ * further observation later in the same walk.
+ *
+ * The live entries of every row must ascend in keyframe slot on entry.  The host entries refuse a row that does not,
+ * a keyframe twice in a row and a point twice in a keyframe's row (below kf_n); on the device entries the result is
+ * then unspecified, but every store stays inside its table.
+ *
+ * orbmm_add_keyframe_observations(cur): for i < kf_n[cur] with p = kf_mappoint[cur][i] not null and not bad: if p does
+ * not observe cur, AddObservation(p, cur, i) and p joins `added`; otherwise p joins `recent_out` (the stereo points
+ * Tracking inserted: append them to recentAddedMapPoints_).  Both lists ascend in i, hold kf_cap entries, -1 padded;
+ * counts[0] / counts[1] are their lengths.  status[i] (kf_cap entries): ORBMM_OK, or ORBMM_OBS_OVERFLOW when p's row
+ * was full: that point is in neither list, the others still apply.  A grid kernel (the points of a row are distinct)
+ * and a one-workgroup stable compaction.  `added` is what UpdateNormalAndDepth and the distinctive descriptors follow
+ * over.
+ *
+ * orbmm_fuse_apply walks an orbm_fuse_batch-shaped list: item i is keyframe item_kf[i] with the entries
+ * [mp_begin[i], mp_begin[i + 1]); point[m] is a map point slot or -1, best_idx[m] what orbm_fuse_device left.  The
+ * items in order, the entries of an item in order:
+ *   ORBMM_APPLY_FUSE: skipped if best_idx < 0, mp_bad[point] or the point observes the keyframe (the test of
+ *     ORBmatcher.cc:876 evaluated again at the entry's turn).  in_kf = kf_mappoint[kf][best_idx].  If there is one and
+ *     it is not bad: Replace(point -> in_kf) when mp_nobs[in_kf] > mp_nobs[point], else Replace(in_kf -> point).  If
+ *     there is none: AddObservation(point, kf, best_idx) and kf_mappoint[kf][best_idx] = point.
+ *   ORBMM_APPLY_FUSE_SIM3: phase 0 skips on best_idx < 0 or mp_bad[point] only; replace_point[m] = in_kf when in_kf is
+ *     there and not bad, AddObservation / AddMapPoint when there is none.  Phase 1, after the item's whole list: for
+ *     every replace_point[m] >= 0 in order, Replace(replace_point[m] -> point[m]).  replace_point: -1 on entry.
+ *   ORBMM_APPLY_LOOP_MATCHED: best_idx[m] is the keypoint index, point[m] the matched loop point (-1: none).
+ *     Replace(kf_mappoint[kf][best_idx] -> point) when the keyframe holds a point there, bad or not; otherwise
+ *     kf_mappoint[kf][best_idx] = point and AddObservation(point, kf, best_idx).
+ * n_fused[i]: the reference's nFused of item i (the entries past the skips; the matched entries in the third mode).
+ * touched[0 .. *n_touched): ascending, the points the reference calls ComputeDistinctiveDescriptors on during the walk
+ * that are not bad at its end: every Replace survivor, and the added points of the third mode.  The rest of touched, up
+ * to n_mappoints entries, is -1: orbmm_update_normal_depth_device with point = touched and n_points = n_mappoints skips
+ * the padding, so the count need not cross PCIe.  progress[4] = {item,
+ * phase, entry within the item, the point whose row was full}: input and output, zero on the first call.  A walk that
+ * ends: *status = ORBMM_OK, progress = {n_items, 0, 0, -1}.  A step that does not fit: the walk stops before it, the
+ * tables hold exactly the steps before it, *status = ORBMM_OBS_OVERFLOW and progress names the step.  Grow the rows
+ * and call again with the same progress, replace_point, n_fused, touched and n_touched: the result equals an
+ * uninterrupted walk on rows that were large enough.
+ * One launch of one workgroup of four wavefronts: the lanes scan the list in chunks and compact the hits into LDS in
+ * order; the hits are taken one after another, every state-dependent test on uniformly loaded values; IsInKeyFrame,
+ * the union and the kf_mappoint stores are spread over all lanes, barriers between the phases; a last scan turns the
+ * touched flags into the list.  No HBM atomics and no floating-point arithmetic: two runs are byte-identical.
+ *
+ * orbmm_grow_observations: the CSR with every row its live entries (not -1) in order followed by `slack` free entries
+ * (extra[p] instead where extra is given; a negative extra counts as 0), into out_off (n_mappoints + 1) and out_kf /
+ * out_idx (n_obs_out entries each, distinct from the inputs).  *status = ORBMM_OBS_OVERFLOW when the total exceeds
+ * n_obs_out: nothing is written at or past n_obs_out, and offsets past it read n_obs_out + 1.  With slack 0 this is
+ * orbmm_compact_observations.  Count per point, one scan by one workgroup (64-bit sums), fill.
+ *
+ * Workspace (per thread, grow-only): kf_cap bytes; 4 * (3 * n_obs + n_mappoints) bytes for the walk.
+ * ---------------------------------------------------------------------------------------- */
+#define ORBMM_OBS_OVERFLOW 2
+#define ORBMM_APPLY_FUSE 0
+#define ORBMM_APPLY_FUSE_SIM3 1
+#define ORBMM_APPLY_LOOP_MATCHED 2
+
+typedef struct orbmm_observe {
+    int32_t n_keyframes, n_mappoints, kf_cap;
+    int32_t n_obs;                    /* entries of mp_obs_kf / mp_obs_idx (>= mp_obs_off[n_mappoints]) */
+    /* orbmm_add_keyframe_observations does not read the arrays marked R; they may be NULL there */
+    const int32_t* kf_n;              /* [K] */
+    int32_t*       kf_mappoint;       /* [K][kf_cap] updated */
+    const float*   kf_uright;         /* [K][kf_cap] */
+    uint8_t*       mp_bad;            /* [M] updated */
+    int32_t*       mp_nobs;           /* [M] updated */
+    int32_t*       mp_found;          /* [M] R, updated */
+    int32_t*       mp_visible;        /* [M] R, updated */
+    int32_t*       mp_replaced;       /* [M] R replaced_ as a slot, -1 for none; updated */
+    const int32_t* mp_obs_off;        /* [M + 1] */
+    int32_t*       mp_obs_kf;         /* updated */
+    int32_t*       mp_obs_idx;        /* updated */
+} orbmm_observe;
+
+typedef struct orbmm_apply {
+    int32_t mode;                     /* ORBMM_APPLY_* */
+    int32_t n_items, n_entries;       /* n_entries: entries of point / best_idx / replace_point (>= mp_begin[n_items]) */
+    const int32_t* item_kf;           /* [n_items] keyframe slots */
+    const int32_t* mp_begin;          /* [n_items + 1] */
+    const int32_t* point;             /* [n_entries] */
+    const int32_t* best_idx;          /* [n_entries] */
+    int32_t* replace_point;           /* [n_entries] ORBMM_APPLY_FUSE_SIM3 only: -1 on the first call, updated */
+    int32_t* n_fused;                 /* [n_items] written from the item the walk starts at */
+    int32_t* touched;                 /* [M] */
+    int32_t* n_touched;               /* [1] read when progress is not zero */
+    int32_t* progress;                /* [4] input and output */
+    int32_t* status;                  /* [1] ORBMM_OK or ORBMM_OBS_OVERFLOW */
+} orbmm_apply;
+
+/* Device forms: every array in HBM (the structs themselves are host memory); enqueue only on `stream`, nothing is copied
+ * back.  ORB_EINVAL for a NULL required array, negative sizes, kf_cap < 1, an unknown mode and a table of 2^31 entries or
+ * more.  The workspace belongs to the calling thread: its calls must be stream-ordered. */
+int orbmm_add_keyframe_observations_device(const orbmm_observe* t, int32_t cur, int32_t* added, int32_t* recent_out,
+                                           int32_t* counts, int32_t* status, void* stream);
+int orbmm_fuse_apply_device(const orbmm_observe* t, const orbmm_apply* a, void* stream);
+int orbmm_grow_observations_device(int32_t n_mappoints, int32_t n_obs, const int32_t* mp_obs_off, const int32_t* mp_obs_kf,
+                                   const int32_t* mp_obs_idx, int32_t slack, const int32_t* extra, int32_t n_obs_out,
+                                   int32_t* out_off, int32_t* out_kf, int32_t* out_idx, int32_t* status, void* stream);
+/* Host forms: every pointer is host memory, synchronous; the updated arrays are written back.  Before anything is
+ * copied, besides the checks above: the offsets start at 0, do not decrease and end within n_obs; mp_obs_kf in
+ * [-1, n_keyframes) (-1 is the slack) and mp_obs_idx of a live entry in [0, kf_cap); the live entries of a row strictly
+ * ascending (a keyframe twice in a row included); kf_n in [0, kf_cap], kf_mappoint in [-1, n_mappoints), no point twice
+ * in a keyframe's row, mp_replaced in [-1, n_mappoints); cur and item_kf in [0, n_keyframes), mp_begin a CSR within
+ * n_entries, point and replace_point in [-1, n_mappoints), best_idx in [-1, kf_cap), progress inside the list, the
+ * touched list of a resumed walk in [0, n_mappoints), extra not negative.  ORB_EINVAL otherwise. */
+int orbmm_add_keyframe_observations(const orbmm_observe* t, int32_t cur, int32_t* added, int32_t* recent_out,
+                                    int32_t* counts, int32_t* status, int device);
+int orbmm_fuse_apply(const orbmm_observe* t, const orbmm_apply* a, int device);
+int orbmm_grow_observations(int32_t n_mappoints, int32_t n_obs, const int32_t* mp_obs_off, const int32_t* mp_obs_kf,
+                            const int32_t* mp_obs_idx, int32_t slack, const int32_t* extra, int32_t n_obs_out,
+                            int32_t* out_off, int32_t* out_kf, int32_t* out_idx, int32_t* status, int device);
+
 const char* orb_last_error(void);
 int orb_device_count(void);
 

@@ -917,6 +917,41 @@ private:
     orbmm_cull tables_;
 };
 
+// The insert half of the observation graph (src/MapPoint.cc:109-122, 191-230): the host owns the arrays of orbmm_observe
+// in HBM and enqueues ProcessNewKeyFrame's loop, the apply loop after each Fuse search and CorrectLoop's matched points on
+// the stream the searches and the map-maintenance calls run on; best_idx never comes back to the host.  A row needs free
+// entries (-1) for an insert: on ORBMM_OBS_OVERFLOW in *d_status, Grow and call FuseApply again with the same arrays.
+class Observations {
+public:
+    explicit Observations(const orbmm_observe& tables) : tables_(tables) {}
+
+    // LocalMapping.cc:309-326 for keyframe slot cur: d_added / d_recent hold kf_cap entries (-1 padded), d_counts their two
+    // lengths, d_status kf_cap entries (ORBMM_OBS_OVERFLOW where a point's row was full)
+    void AddKeyFrameObservations(int32_t cur, int32_t* d_added, int32_t* d_recent, int32_t* d_counts, int32_t* d_status,
+                                 void* stream = nullptr) const {
+        check(orbmm_add_keyframe_observations_device(&tables_, cur, d_added, d_recent, d_counts, d_status, stream),
+              "orbmm_add_keyframe_observations_device");
+    }
+    // the apply loop of apply.mode over the list orbm_fuse_device left in HBM
+    void FuseApply(const orbmm_apply& apply, void* stream = nullptr) const {
+        check(orbmm_fuse_apply_device(&tables_, &apply, stream), "orbmm_fuse_apply_device");
+    }
+    // the observation CSR with `slack` free entries per row (d_extra[p] where given) into arrays of n_obs_out entries; the
+    // caller swaps them and updates tables()
+    void Grow(int32_t slack, const int32_t* d_extra, int32_t n_obs_out, int32_t* d_out_off, int32_t* d_out_kf, int32_t* d_out_idx,
+              int32_t* d_status, void* stream = nullptr) const {
+        check(orbmm_grow_observations_device(tables_.n_mappoints, tables_.n_obs, tables_.mp_obs_off, tables_.mp_obs_kf,
+                                             tables_.mp_obs_idx, slack, d_extra, n_obs_out, d_out_off, d_out_kf, d_out_idx, d_status,
+                                             stream),
+              "orbmm_grow_observations_device");
+    }
+    orbmm_observe& tables() { return tables_; }
+    const orbmm_observe& tables() const { return tables_; }
+
+private:
+    orbmm_observe tables_;
+};
+
 }  // namespace ORB_SLAM2_AMD
 
 #endif  // ORBSLAM2_AMD_HPP

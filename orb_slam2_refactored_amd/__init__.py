@@ -25,6 +25,9 @@ Host mirrors of the reference's interfaces (tiantianxuabc/ORB_SLAM2_Refactored):
   MapPointCulling / KeyFrameCulling <- LocalMapping::MapPointCulling and KeyFrameCulling (src/LocalMapping.cc:335-369,
                                      641-701) with MapPoint::SetBadFlag / EraseObservation and KeyFrame::SetBadFlag,
                                      CompactObservations and LiveChildren, culling.py
+  AddKeyFrameObservations / FuseApply <- MapPoint::AddObservation and Replace (src/MapPoint.cc:109-122, 191-230) under
+                                     ProcessNewKeyFrame's loop, Fuse's apply loops and CorrectLoop's matched points, with
+                                     GrowObservations, observations.py
 All compute runs in liborbslam2_amd.so (HIP kernels behind include/orbslam2_amd.h).
 """
 from .extractor import ORBextractor, KP_DTYPE
@@ -43,9 +46,12 @@ from .map_maintenance import (UpdateNormalAndDepth, update_normal_depth_device, 
                               update_connections_device, Children, children_device, CovisCsr, covis_csr_device)
 from .culling import (MapPointCulling, map_point_culling_device, KeyFrameCulling, keyframe_culling_device,
                       CompactObservations, compact_observations_device, LiveChildren, live_children_device)
+from .observations import (AddKeyFrameObservations, add_keyframe_observations_device, FuseApply, fuse_apply_device,
+                           GrowObservations, grow_observations_device)
 from .synth import synth_image, shifted_pair, stereo_pair, make_pose_batch
 
-__all__ = ["MapPointCulling", "map_point_culling_device", "KeyFrameCulling", "keyframe_culling_device", "CompactObservations",
+__all__ = ["AddKeyFrameObservations", "add_keyframe_observations_device", "FuseApply", "fuse_apply_device", "GrowObservations",
+           "grow_observations_device", "MapPointCulling", "map_point_culling_device", "KeyFrameCulling", "keyframe_culling_device", "CompactObservations",
            "compact_observations_device", "LiveChildren", "live_children_device", "KeyFrameDatabase", "LocalMap", "UpdateNormalAndDepth", "update_normal_depth_device", "UpdateConnections",
            "update_connections_device", "Children", "children_device", "CovisCsr", "covis_csr_device", "PreparePairs", "TriangulateMatches", "CreateNewMapPoints", "prepare_pairs_device", "triangulate_matches_device",
            "create_new_map_points_device", "InitializerInitialize", "initializer_initialize_device", "make_initializer_draws", "PnPsolverIterate", "pnpsolver_iterate_device", "make_pnp_draws", "Sim3SolverIterate", "sim3solver_iterate_device", "make_draws", "ORBextractor", "ORBmatcher", "ComputeStereoMatches", "Fuse", "fuse_device", "SearchByProjectionSim3",

@@ -345,6 +345,20 @@ class OrbmmGraph(C.Structure):
                                   "kf_parent", "kf_covis", "status")]
 
 
+class OrbmmObserve(C.Structure):
+    """orbmm_observe (include/orbslam2_amd.h)."""
+    _fields_ = [("n_keyframes", C.c_int32), ("n_mappoints", C.c_int32), ("kf_cap", C.c_int32), ("n_obs", C.c_int32)] + [
+        (k, C.c_void_p) for k in ("kf_n", "kf_mappoint", "kf_uright", "mp_bad", "mp_nobs", "mp_found", "mp_visible",
+                                  "mp_replaced", "mp_obs_off", "mp_obs_kf", "mp_obs_idx")]
+
+
+class OrbmmApply(C.Structure):
+    """orbmm_apply (include/orbslam2_amd.h)."""
+    _fields_ = [("mode", C.c_int32), ("n_items", C.c_int32), ("n_entries", C.c_int32)] + [
+        (k, C.c_void_p) for k in ("item_kf", "mp_begin", "point", "best_idx", "replace_point", "n_fused", "touched",
+                                  "n_touched", "progress", "status")]
+
+
 class OrbmmCsr(C.Structure):
     """orbmm_csr (include/orbslam2_amd.h)."""
     _fields_ = [("kf_bad", C.c_void_p), ("covis_begin", C.c_void_p), ("covis_slot", C.c_void_p),
@@ -478,6 +492,12 @@ SIGNATURES = {    "orbx_create": (C.c_int, [C.POINTER(OrbxParams), C.c_int, C.PO
     "orbmm_compact_observations": (C.c_int, [C.c_int32, C.c_int32, VP, VP, VP, VP, VP, VP, C.c_int]),
     "orbmm_children_live_device": (C.c_int, [C.c_int32, VP, VP, VP, VP, VP]),
     "orbmm_children_live": (C.c_int, [C.c_int32, VP, VP, VP, VP, C.c_int]),
+    "orbmm_add_keyframe_observations_device": (C.c_int, [C.POINTER(OrbmmObserve), C.c_int32, VP, VP, VP, VP, VP]),
+    "orbmm_add_keyframe_observations": (C.c_int, [C.POINTER(OrbmmObserve), C.c_int32, VP, VP, VP, VP, C.c_int]),
+    "orbmm_fuse_apply_device": (C.c_int, [C.POINTER(OrbmmObserve), C.POINTER(OrbmmApply), VP]),
+    "orbmm_fuse_apply": (C.c_int, [C.POINTER(OrbmmObserve), C.POINTER(OrbmmApply), C.c_int]),
+    "orbmm_grow_observations_device": (C.c_int, [C.c_int32, C.c_int32, VP, VP, VP, C.c_int32, VP, C.c_int32, VP, VP, VP, VP, VP]),
+    "orbmm_grow_observations": (C.c_int, [C.c_int32, C.c_int32, VP, VP, VP, C.c_int32, VP, C.c_int32, VP, VP, VP, VP, C.c_int]),
     "orbx_pack_descriptors": (C.c_int,[VP, C.c_int, VP, VP, C.c_int, VP, C.c_int, VP]),
     "orbx_profile_enable": (C.c_int, [VP, C.c_int]),
     "orbx_profile_read": (C.c_int, [VP, VP, VP]),

@@ -19,6 +19,8 @@
 //   mm_cull_keyframes_kernel  one workgroup walks the targets in order: all lanes over the target's row for the count and
 //                             for EraseObservation, one wavefront per neighbour for EraseConnection, one for the tree
 //   mm_compact_*_kernel       the observation CSR without erased entries: count per point, one scan, fill
+// The observation edits (MapPoint::AddObservation / Replace and the loops that call them; the rules are
+// csrc/mm_observe.h's) are orbmm_observe.inc, included at the end.
 #include <algorithm>
 #include <cstdlib>
 #include <vector>
@@ -918,3 +920,5 @@ extern "C" int orbmm_children_live(int32_t n_keyframes, const int32_t* kf_parent
     ORB_HIP_TRY(hipStreamSynchronize(nullptr));
     return io.download();
 }
+
+#include "orbmm_observe.inc"
