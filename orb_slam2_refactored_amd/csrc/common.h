@@ -7,6 +7,7 @@
 #include <cstdio>
 #include <string>
 
+#include "host_mirror.h"
 #include "orbslam2_amd.h"
 
 namespace orbamd {
@@ -68,5 +69,71 @@ struct DevBuf {
 };
 
 inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
+
+using orbamd_host::Carver;
+
+// A module's per-thread device buffers: ws is the _device entries' workspace, io the slab the host entries stage in.
+// Both are dropped when the thread moves to another device.
+struct Scratch {
+    DevBuf ws, io;
+    int device = -1;
+    int use_device(int dev) {
+        if (device != dev) {
+            ws.release();
+            io.release();
+            device_changed();
+            device = dev;
+        }
+        return ORB_OK;
+    }
+    int use_current_device() {
+        int dev = 0;
+        ORB_HIP_TRY(hipGetDevice(&dev));
+        return use_device(dev);
+    }
+
+protected:
+    virtual void device_changed() {}   // what else a module keeps on the device
+};
+
+// host_mirror.h's plan with synchronous HIP copies.
+struct Mirror : orbamd_host::Mirror {
+    Mirror() : orbamd_host::Mirror(to_device, to_host) {}
+    static int to_device(void* dst, const void* src, size_t bytes) {
+        ORB_HIP_TRY(hipMemcpy(dst, src, bytes, hipMemcpyHostToDevice));
+        return ORB_OK;
+    }
+    static int to_host(void* dst, const void* src, size_t bytes) {
+        ORB_HIP_TRY(hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost));
+        return ORB_OK;
+    }
+};
+
+// The tail of every host entry, after its checks: the fields m holds are staged in s.io, device_call() runs the _device
+// entry on the null stream with the re-bound arguments, and the outputs come back after one synchronisation.
+template <class Fn>
+int run_host(Scratch& s, int device, Mirror& m, Fn device_call) {
+    ORB_HIP_TRY(hipSetDevice(device));
+    int rc;
+    if ((rc = s.use_device(device))) return rc;
+    if ((rc = m.upload(s.io))) return rc;
+    if ((rc = device_call())) return rc;
+    ORB_HIP_TRY(hipStreamSynchronize(nullptr));
+    return m.download();
+}
+
+// CSR offsets off[0 .. n]: start at 0, do not decrease, end at n_obs at most.
+inline int check_csr(const int32_t* off, int n, int n_obs, const char* what) {
+    ORB_CHECK_ARG(off[0] == 0, std::string(what) + ": offsets must start at 0");
+    for (int i = 0; i < n; i++) ORB_CHECK_ARG(off[i + 1] >= off[i], std::string(what) + ": offsets must not decrease");
+    ORB_CHECK_ARG(off[n] <= n_obs, std::string(what) + ": offsets end past n_obs");
+    return ORB_OK;
+}
+
+// a[0 .. n) in [lo, hi)
+inline int check_range(const int32_t* a, size_t n, int lo, int hi, const char* msg) {
+    for (size_t i = 0; i < n; i++) ORB_CHECK_ARG(a[i] >= lo && a[i] < hi, msg);
+    return ORB_OK;
+}
 
 }  // namespace orbamd

@@ -1,7 +1,8 @@
 // KeyFrame::UpdateConnections with AddConnection / UpdateBestCovisibles (src/KeyFrame.cc:94-119, 235-309) on slot
 // tables: which observers count, which counts are pairs, the walk of one target keyframe through a batch and the two
 // sorts.  Integer rules only.  Compiles for host and device; every routine is written for a group G of lanes that
-// share the work: MmOne (one lane, below) on the CPU, one wavefront in orbmm.hip.  A group gives lane, width, sync(),
+// share the work: MmOne (one lane, below) on the CPU, one wavefront in orbmm.hip (the device groups are
+// mm_groups.h's).  A group gives lane, width, sync(),
 // the reductions sum / min / max over its lanes and prefix(flag, total): the number of set flags on lower lanes.
 // Every branch on a reduced value or on a value all lanes load from one address is taken by the whole group.
 //

@@ -1,6 +1,7 @@
 // MapPoint::UpdateNormalAndDepth (src/MapPoint.cc:341-380) for one point of a slot-table map, in the reference's float
 // arithmetic and one fixed order.  Compiles for host and device (-ffp-contract=off, as the whole library): orbmm.hip
-// runs it one lane per point, tests/native/map_maintenance_check.cpp on the CPU, tests/map_maintenance_ref.py restates
+// (its host entry stages through common.h's Mirror, its buffers are mm_host.h's) runs it one lane per point,
+// tests/native/map_maintenance_check.cpp on the CPU, tests/map_maintenance_ref.py restates
 // it in numpy.
 //   Ow            (-R^T) t as CameraPose::Invt: a cv::Matx product, s = 0, s += a(i, k) b(k), k ascending, in float.
 //   Normalized    (1. / cv::norm(v)) v: the squares summed in double, ascending (norm3.h); 1. / norm in double; each

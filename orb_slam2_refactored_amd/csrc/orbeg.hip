@@ -400,18 +400,7 @@ __global__ __launch_bounds__(64) void eg_recover_kernel(EGDev g) {
     }
 }
 
-struct EGScratch {
-    DevBuf ws, io;
-    int device = -1;
-    void use_device(int dev) {
-        if (device != dev) {
-            ws.release();
-            io.release();
-            device = dev;
-        }
-    }
-};
-thread_local EGScratch g_eg;
+thread_local Scratch g_eg;
 thread_local float* g_eg_stage_ms = nullptr;   // orbba_essential_graph_profile: per-kernel device time
 
 enum { EG_K_SETUP, EG_K_MEASURE, EG_K_LINEARIZE, EG_K_ASSEMBLE, EG_K_BEGIN, EG_K_STAGE, EG_K_SOLVE, EG_K_UPDATE,
@@ -439,38 +428,32 @@ extern "C" int orbba_optimize_essential_graph_device(const orbba_essential_graph
                                                      void* stream) {
     int rc;
     if ((rc = eg_common(in, out))) return rc;
-    int dev = 0;
-    ORB_HIP_TRY(hipGetDevice(&dev));
-    g_eg.use_device(dev);
+    if ((rc = g_eg.use_current_device())) return rc;
     hipStream_t st = (hipStream_t)stream;
     const size_t V = in->n_keyframes, E = in->n_edges, E1 = std::max<size_t>(E, 1);
     const size_t Dmax = 7 * V, Dpm = solve_dp((int)Dmax);
-    size_t off = 0;
-    auto take = [&](size_t bytes) { const size_t o = off; off += align_up(std::max<size_t>(bytes, 1), 256); return o; };
-    const size_t o_ctl = take(sizeof(EGCtl)), o_est = take(V * 64), o_sv = take(V * 64), o_meas = take(E1 * 64),
-                 o_J = take(E1 * 98 * 8), o_err = take(E1 * 56), o_chi = take(E1 * 8), o_chit = take(E1 * 8),
-                 o_H = take(Dmax * Dmax * 8), o_b = take(Dmax * 8), o_x = take(Dmax * 8), o_Sg = take(Dpm * (Dpm + 1) * 8),
-                 o_vmap = take(V * 4), o_vbeg = take((V + 1) * 4), o_vlist = take(2 * E1 * 4), o_eok = take(E1);
-    if ((rc = g_eg.ws.reserve(off))) return rc;
-    char* w = g_eg.ws.as<char>();
     EGDev g;
     memset(&g, 0, sizeof(g));
+    auto carve = [&](char* base) {
+        Carver c{base};
+        c.take(g.ctl, 1); c.take(g.est, V * 8); c.take(g.est_sv, V * 8); c.take(g.meas, E1 * 8); c.take(g.J, E1 * 98);
+        c.take(g.err, E1 * 7); c.take(g.chi, E1); c.take(g.chi_t, E1); c.take(g.H, Dmax * Dmax); c.take(g.b, Dmax);
+        c.take(g.x, Dmax); c.take(g.Sg, Dpm * (Dpm + 1)); c.take(g.vmap, V); c.take(g.vbeg, V + 1); c.take(g.vlist, 2 * E1);
+        c.take(g.eok, E1);
+        return c.off;
+    };
+    if ((rc = g_eg.ws.reserve(carve(nullptr)))) return rc;
+    carve(g_eg.ws.as<char>());
     g.V = (int)V; g.E = (int)E; g.N = in->n_points; g.fixed = in->fixed_slot; g.fix_scale = in->fix_scale != 0;
     g.vs = in->vertex_sim3; g.es = in->edge_sim3; g.ei = in->edge_i; g.ej = in->edge_j; g.et = in->edge_table;
     g.pts = in->points; g.pref = in->point_ref;
-    g.ctl = (EGCtl*)(w + o_ctl); g.est = (double*)(w + o_est); g.est_sv = (double*)(w + o_sv);
-    g.meas = (double*)(w + o_meas); g.J = (double*)(w + o_J); g.err = (double*)(w + o_err);
-    g.chi = (double*)(w + o_chi); g.chi_t = (double*)(w + o_chit); g.H = (double*)(w + o_H);
-    g.b = (double*)(w + o_b); g.x = (double*)(w + o_x); g.Sg = (double*)(w + o_Sg);
-    g.vmap = (int32_t*)(w + o_vmap); g.vbeg = (int32_t*)(w + o_vbeg); g.vlist = (int32_t*)(w + o_vlist);
-    g.eok = (uint8_t*)(w + o_eok);
     g.o_g2o = out->sim3_g2o; g.o_pose = out->pose; g.o_pts = out->points; g.o_meas = out->measurement;
     g.o_iter = out->iterations; g.o_chi2 = out->chi2; g.o_acc = out->accept;
 
     const size_t solve_lds = 3 * Dpm * sizeof(double);
     {
         static thread_local size_t lim[64] = {};
-        size_t& cur = lim[dev & 63];
+        size_t& cur = lim[g_eg.device & 63];
         if (solve_lds > cur) {
             ORB_HIP_TRY(hipFuncSetAttribute((const void*)eg_solve_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
                                             (int)solve_lds));
@@ -566,36 +549,16 @@ static int eg_host(const orbba_essential_graph* in, orbba_essential_graph_result
     if ((rc = eg_common(in, out))) return rc;   // the checks, before any device call
     if ((rc = eg_check_host(in))) return rc;
     const size_t V = in->n_keyframes, E = in->n_edges, N = in->n_points;
-    ORB_HIP_TRY(hipSetDevice(device));
-    g_eg.use_device(device);
-    size_t off = 0;
-    auto take = [&](size_t bytes) { const size_t o = off; off += align_up(std::max<size_t>(bytes, 1), 256); return o; };
-    struct In { const void* src; size_t bytes; size_t at; };
-    In ins[] = {{in->vertex_sim3, V * 52, 0}, {in->edge_sim3, V * 52, 0}, {in->edge_i, E * 4, 0}, {in->edge_j, E * 4, 0},
-                {in->edge_table, E, 0}, {in->points, N * 12, 0}, {in->point_ref, N * 4, 0}};
-    for (In& i : ins) i.at = take(i.bytes);
-    const size_t o_g = take(V * 64), o_p = take(V * 48), o_x = take(N * 12), o_m = take(E * 64), o_it = take(8),
-                 o_c = take(8), o_a = take(ORBBA_EG_MAX_TRIALS);
-    if ((rc = g_eg.io.reserve(off))) return rc;
-    char* b = g_eg.io.as<char>();
-    for (const In& i : ins)
-        if (i.bytes) ORB_HIP_TRY(hipMemcpy(b + i.at, i.src, i.bytes, hipMemcpyHostToDevice));
     orbba_essential_graph d = *in;
-    d.vertex_sim3 = (const float*)(b + ins[0].at); d.edge_sim3 = (const float*)(b + ins[1].at);
-    d.edge_i = (const int32_t*)(b + ins[2].at); d.edge_j = (const int32_t*)(b + ins[3].at);
-    d.edge_table = (const uint8_t*)(b + ins[4].at);
-    d.points = (const float*)(b + ins[5].at); d.point_ref = (const int32_t*)(b + ins[6].at);
-    orbba_essential_graph_result r{(double*)(b + o_g), (float*)(b + o_p), (float*)(b + o_x), (double*)(b + o_m),
-                                   (int32_t*)(b + o_it), (double*)(b + o_c), (uint8_t*)(b + o_a)};
-    if ((rc = orbba_optimize_essential_graph_device(&d, &r, nullptr))) return rc;
-    ORB_HIP_TRY(hipMemcpy(out->sim3_g2o, r.sim3_g2o, V * 64, hipMemcpyDeviceToHost));   // (synchronises with the null stream)
-    ORB_HIP_TRY(hipMemcpy(out->pose, r.pose, V * 48, hipMemcpyDeviceToHost));
-    if (N) ORB_HIP_TRY(hipMemcpy(out->points, r.points, N * 12, hipMemcpyDeviceToHost));
-    if (out->measurement && E) ORB_HIP_TRY(hipMemcpy(out->measurement, r.measurement, E * 64, hipMemcpyDeviceToHost));
-    ORB_HIP_TRY(hipMemcpy(out->iterations, r.iterations, 8, hipMemcpyDeviceToHost));
-    ORB_HIP_TRY(hipMemcpy(out->chi2, r.chi2, 8, hipMemcpyDeviceToHost));
-    ORB_HIP_TRY(hipMemcpy(out->accept, r.accept, ORBBA_EG_MAX_TRIALS, hipMemcpyDeviceToHost));
-    return ORB_OK;
+    orbba_essential_graph_result r = *out;
+    Mirror io;
+    io.add(d.vertex_sim3, V * 13, true, false); io.add(d.edge_sim3, V * 13, true, false); io.add(d.edge_i, E, true, false);
+    io.add(d.edge_j, E, true, false); io.add(d.edge_table, E, true, false); io.add(d.points, N * 3, true, false);
+    io.add(d.point_ref, N, true, false);
+    io.add(r.sim3_g2o, V * 8, false, true); io.add(r.pose, V * 12, false, true); io.add(r.points, N * 3, false, true);
+    io.add(r.measurement, E * 8, false, true); io.add(r.iterations, 2, false, true); io.add(r.chi2, 1, false, true);
+    io.add(r.accept, ORBBA_EG_MAX_TRIALS, false, true);
+    return run_host(g_eg, device, io, [&] { return orbba_optimize_essential_graph_device(&d, &r, nullptr); });
 }
 
 extern "C" int orbba_optimize_essential_graph(const orbba_essential_graph* in, orbba_essential_graph_result* out,

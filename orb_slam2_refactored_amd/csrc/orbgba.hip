@@ -109,18 +109,7 @@ __global__ __launch_bounds__(256) void gba_points_kernel(GbaDev g) {
 
 namespace {
 
-struct GbaScratch {
-    DevBuf ws, io;
-    int device = -1;
-    void use_device(int dev) {
-        if (device != dev) {
-            ws.release();
-            io.release();
-            device = dev;
-        }
-    }
-};
-thread_local GbaScratch g_gba;
+thread_local Scratch g_gba;
 
 int gba_common(const orbba_gba_map* m) {
     ORB_CHECK_ARG(m, "null argument");
@@ -182,9 +171,7 @@ extern "C" int orbba_gba_update_map_device(const orbba_gba_map* m, void* stream)
     int rc;
     if ((rc = gba_common(m))) return rc;
     const int K = m->n_keyframes, M = m->n_mappoints;
-    int dev = 0;
-    ORB_HIP_TRY(hipGetDevice(&dev));
-    g_gba.use_device(dev);
+    if ((rc = g_gba.use_current_device())) return rc;
     hipStream_t st = (hipStream_t)stream;
     const size_t kw = align_up(std::max<size_t>(K, 1) * 4, 256);
     if ((rc = g_gba.ws.reserve(3 * kw))) return rc;
@@ -202,31 +189,12 @@ extern "C" int orbba_gba_update_map(const orbba_gba_map* m, int device) {
     int rc;
     if ((rc = gba_common(m)) || (rc = gba_check_host(m))) return rc;   // the checks, before any device call
     const size_t K = m->n_keyframes, M = m->n_mappoints, C = m->kf_child_off[K];
-    ORB_HIP_TRY(hipSetDevice(device));
-    g_gba.use_device(device);
-    size_t off = 0;
-    auto take = [&](size_t bytes) { const size_t o = off; off += align_up(std::max<size_t>(bytes, 1), 256); return o; };
-    struct Arr { const void* src; void* back; size_t bytes; size_t at; };   // back: copied to the caller afterwards
-    Arr a[] = {{m->origins, nullptr, (size_t)m->n_origins * 4, 0}, {m->kf_child_off, nullptr, (K + 1) * 4, 0},
-               {m->kf_child_idx, nullptr, C * 4, 0},               {m->kf_in_gba, m->kf_in_gba, K, 0},
-               {m->kf_pose, m->kf_pose, K * 48, 0},                {m->kf_pose_gba, m->kf_pose_gba, K * 48, 0},
-               {m->kf_pose_bef, m->kf_pose_bef, K * 48, 0},        {m->mp_bad, nullptr, M, 0},
-               {m->mp_in_gba, nullptr, M, 0},                      {m->mp_pos_gba, nullptr, M * 12, 0},
-               {m->mp_ref_kf, nullptr, M * 4, 0},                  {m->mp_xw, m->mp_xw, M * 12, 0}};
-    for (Arr& x : a) x.at = take(x.bytes);
-    if ((rc = g_gba.io.reserve(off))) return rc;
-    char* b = g_gba.io.as<char>();
-    for (const Arr& x : a)
-        if (x.bytes) ORB_HIP_TRY(hipMemcpy(b + x.at, x.src, x.bytes, hipMemcpyHostToDevice));
     orbba_gba_map d = *m;
-    d.origins = (const int32_t*)(b + a[0].at); d.kf_child_off = (const int32_t*)(b + a[1].at);
-    d.kf_child_idx = (const int32_t*)(b + a[2].at); d.kf_in_gba = (uint8_t*)(b + a[3].at);
-    d.kf_pose = (float*)(b + a[4].at); d.kf_pose_gba = (float*)(b + a[5].at); d.kf_pose_bef = (float*)(b + a[6].at);
-    d.mp_bad = (const uint8_t*)(b + a[7].at); d.mp_in_gba = (const uint8_t*)(b + a[8].at);
-    d.mp_pos_gba = (const float*)(b + a[9].at); d.mp_ref_kf = (const int32_t*)(b + a[10].at);
-    d.mp_xw = (float*)(b + a[11].at);
-    if ((rc = orbba_gba_update_map_device(&d, nullptr))) return rc;
-    for (const Arr& x : a)   // (each copy synchronises with the null stream)
-        if (x.back && x.bytes) ORB_HIP_TRY(hipMemcpy(x.back, b + x.at, x.bytes, hipMemcpyDeviceToHost));
-    return ORB_OK;
+    Mirror io;
+    io.add(d.origins, (size_t)m->n_origins, true, false); io.add(d.kf_child_off, K + 1, true, false);
+    io.add(d.kf_child_idx, C, true, false); io.add(d.kf_in_gba, K, true, true); io.add(d.kf_pose, K * 12, true, true);
+    io.add(d.kf_pose_gba, K * 12, true, true); io.add(d.kf_pose_bef, K * 12, true, true); io.add(d.mp_bad, M, true, false);
+    io.add(d.mp_in_gba, M, true, false); io.add(d.mp_pos_gba, M * 3, true, false); io.add(d.mp_ref_kf, M, true, false);
+    io.add(d.mp_xw, M * 3, true, true);
+    return run_host(g_gba, device, io, [&] { return orbba_gba_update_map_device(&d, nullptr); });
 }

@@ -454,18 +454,7 @@ __global__ __launch_bounds__(64) void ini_finish_kernel(IniArgs a) {
     }
 }
 
-struct IniScratch {
-    DevBuf ws, io;
-    int device = -1;
-    void use_device(int dev) {
-        if (device != dev) {
-            ws.release();
-            io.release();
-            device = dev;
-        }
-    }
-};
-thread_local IniScratch g_ini;
+thread_local Scratch g_ini;
 
 }  // namespace orbamd
 
@@ -513,24 +502,16 @@ extern "C" int orb_initializer_initialize_device(const orb_initializer_batch* in
     int rc;
     if ((rc = ini_common(in, out, a))) return rc;
     if (in->n_pairs == 0) return ORB_OK;
-    int dev = 0;
-    ORB_HIP_TRY(hipGetDevice(&dev));
-    g_ini.use_device(dev);
+    if ((rc = g_ini.use_current_device())) return rc;
     const size_t K1 = std::max<size_t>(in->total_kp1, 1), F = in->n_pairs, T = in->max_iterations;
-    size_t off = 0;
-    auto take = [&](size_t bytes) { const size_t o = off; off += align_up(bytes, 256); return o; };
-    const size_t o_recs = take(K1 * sizeof(IniRec)), o_info = take(F * 16), o_tnorm = take(F * 32), o_sets = take(F * T * 32),
-                 o_mat = take(F * 2 * T * 36), o_p3d = take(8 * K1 * 12), o_flag = take(8 * K1), o_rt = take(F * 8 * 48);
-    if ((rc = g_ini.ws.reserve(off))) return rc;
-    char* w = g_ini.ws.as<char>();
-    a.recs = (IniRec*)(w + o_recs);
-    a.info = (int32_t*)(w + o_info);
-    a.tnorm = (float*)(w + o_tnorm);
-    a.sets = (int32_t*)(w + o_sets);
-    a.hyp_mat = (float*)(w + o_mat);
-    a.cand_p3d = (float*)(w + o_p3d);
-    a.cand_flag = (uint8_t*)(w + o_flag);
-    a.cand_rt = (float*)(w + o_rt);
+    auto carve = [&](char* base) {
+        Carver c{base};
+        c.take(a.recs, K1); c.take(a.info, F * 4); c.take(a.tnorm, F * 8); c.take(a.sets, F * T * 8);
+        c.take(a.hyp_mat, F * 2 * T * 9); c.take(a.cand_p3d, 8 * K1 * 3); c.take(a.cand_flag, 8 * K1); c.take(a.cand_rt, F * 8 * 12);
+        return c.off;
+    };
+    if ((rc = g_ini.ws.reserve(carve(nullptr)))) return rc;
+    carve(g_ini.ws.as<char>());
     const hipStream_t st = (hipStream_t)stream;
     const int waves = (in->max_iterations + 63) / 64;
     hipLaunchKernelGGL(ini_prepare_kernel, dim3(a.n_pairs), dim3(64), 0, st, a);
@@ -562,41 +543,17 @@ extern "C" int orb_initializer_initialize(const orb_initializer_batch* in, orb_i
     const size_t n_draws = F * T * 8;
     for (size_t j = 0; j < n_draws; j++)
         ORB_CHECK_ARG(in->draws[j] >= 0 && in->draws[j] <= in->rand_max, "draws must lie in [0, rand_max]");
-    ORB_HIP_TRY(hipSetDevice(device));
-    g_ini.use_device(device);
-    size_t off = 0;
-    auto take = [&](size_t bytes) { const size_t o = off; off += align_up(std::max<size_t>(bytes, 1), 256); return o; };
-    struct Io { const void* src; void* dst; size_t bytes; size_t at; };
-    Io ins[] = {{b1, nullptr, (F + 1) * 4, 0}, {b2, nullptr, (F + 1) * 4, 0}, {in->kp1_xy, nullptr, K1 * 8, 0},
-                {in->kp2_xy, nullptr, K2 * 8, 0}, {in->matches12, nullptr, K1 * 4, 0}, {in->camera, nullptr, F * 16, 0},
-                {in->draws, nullptr, n_draws * 4, 0}};
-    Io outs[] = {{nullptr, out->found, F * 4, 0}, {nullptr, out->model, F * 4, 0}, {nullptr, out->r21t21, F * 48, 0},
-                 {nullptr, out->p3d, K1 * 12, 0}, {nullptr, out->triangulated, K1, 0}, {nullptr, out->score_h, F * 4, 0},
-                 {nullptr, out->score_f, F * 4, 0}, {nullptr, out->best_h, F * 4, 0}, {nullptr, out->best_f, F * 4, 0},
-                 {nullptr, out->h21, F * 36, 0}, {nullptr, out->f21, F * 36, 0}, {nullptr, out->inlier_h, K1, 0},
-                 {nullptr, out->inlier_f, K1, 0}, {nullptr, out->hyp_score, F * 2 * T * 4, 0}, {nullptr, out->n_good, F * 32, 0},
-                 {nullptr, out->parallax, F * 32, 0}};
-    for (Io& i : ins) i.at = take(i.bytes);
-    for (Io& o : outs) o.at = take(o.bytes);
-    if ((rc = g_ini.io.reserve(off))) return rc;
-    char* b = g_ini.io.as<char>();
-    for (const Io& i : ins)
-        if (i.bytes) ORB_HIP_TRY(hipMemcpy(b + i.at, i.src, i.bytes, hipMemcpyHostToDevice));
     orb_initializer_batch d = *in;
-    d.kp1_begin = (const int32_t*)(b + ins[0].at); d.kp2_begin = (const int32_t*)(b + ins[1].at);
-    d.kp1_xy = (const float*)(b + ins[2].at); d.kp2_xy = (const float*)(b + ins[3].at);
-    d.matches12 = (const int32_t*)(b + ins[4].at); d.camera = (const float*)(b + ins[5].at);
-    d.draws = (const int32_t*)(b + ins[6].at);
-    orb_initializer_result r{};
-    r.found = (int32_t*)(b + outs[0].at); r.model = (int32_t*)(b + outs[1].at); r.r21t21 = (float*)(b + outs[2].at);
-    r.p3d = (float*)(b + outs[3].at); r.triangulated = (uint8_t*)(b + outs[4].at);
-    r.score_h = (float*)(b + outs[5].at); r.score_f = (float*)(b + outs[6].at);
-    r.best_h = (int32_t*)(b + outs[7].at); r.best_f = (int32_t*)(b + outs[8].at);
-    r.h21 = (float*)(b + outs[9].at); r.f21 = (float*)(b + outs[10].at);
-    r.inlier_h = (uint8_t*)(b + outs[11].at); r.inlier_f = (uint8_t*)(b + outs[12].at);
-    r.hyp_score = (float*)(b + outs[13].at); r.n_good = (int32_t*)(b + outs[14].at); r.parallax = (float*)(b + outs[15].at);
-    if ((rc = orb_initializer_initialize_device(&d, &r, nullptr))) return rc;
-    for (const Io& o : outs)   // (the first copy synchronises with the null stream)
-        if (o.bytes) ORB_HIP_TRY(hipMemcpy(o.dst, b + o.at, o.bytes, hipMemcpyDeviceToHost));
-    return ORB_OK;
+    orb_initializer_result r = *out;
+    Mirror io;
+    io.add(d.kp1_begin, F + 1, true, false); io.add(d.kp2_begin, F + 1, true, false); io.add(d.kp1_xy, K1 * 2, true, false);
+    io.add(d.kp2_xy, K2 * 2, true, false); io.add(d.matches12, K1, true, false); io.add(d.camera, F * 4, true, false);
+    io.add(d.draws, n_draws, true, false);
+    io.add(r.found, F, false, true); io.add(r.model, F, false, true); io.add(r.r21t21, F * 12, false, true);
+    io.add(r.p3d, K1 * 3, false, true); io.add(r.triangulated, K1, false, true); io.add(r.score_h, F, false, true);
+    io.add(r.score_f, F, false, true); io.add(r.best_h, F, false, true); io.add(r.best_f, F, false, true);
+    io.add(r.h21, F * 9, false, true); io.add(r.f21, F * 9, false, true); io.add(r.inlier_h, K1, false, true);
+    io.add(r.inlier_f, K1, false, true); io.add(r.hyp_score, F * 2 * T, false, true); io.add(r.n_good, F * 8, false, true);
+    io.add(r.parallax, F * 8, false, true);
+    return run_host(g_ini, device, io, [&] { return orb_initializer_initialize_device(&d, &r, nullptr); });
 }

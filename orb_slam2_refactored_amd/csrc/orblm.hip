@@ -191,48 +191,7 @@ __global__ __launch_bounds__(LM_BLOCK) void lm_triangulate_kernel(LmArgs a, LmTa
     if (tid == 0) a.o.n_created[p] = total;
 }
 
-struct LmScratch {
-    DevBuf io;
-    int device = -1;
-    void use_device(int dev) {
-        if (device != dev) {
-            io.release();
-            device = dev;
-        }
-    }
-};
-thread_local LmScratch g_lm;
-
-// Host arrays mirrored in one device slab: add() records a pointer field, go() uploads and points the field at the
-// device copy, back() downloads the outputs.
-struct LmMirror {
-    struct Item { void** field; void* host; size_t bytes; bool in, out; size_t at; };
-    std::vector<Item> items;
-    size_t total = 0;
-    template <class T>
-    void add(T*& field, size_t count, bool in, bool out) {
-        if (!field) return;
-        const size_t bytes = std::max<size_t>(count * sizeof(T), 1);
-        items.push_back(Item{(void**)&field, (void*)field, bytes, in, out, total});
-        total += align_up(bytes, 256);
-    }
-    int go() {
-        int rc;
-        if ((rc = g_lm.io.reserve(std::max<size_t>(total, 256)))) return rc;
-        char* b = g_lm.io.as<char>();
-        for (Item& it : items) {
-            if (it.in) ORB_HIP_TRY(hipMemcpy(b + it.at, it.host, it.bytes, hipMemcpyHostToDevice));
-            *it.field = b + it.at;
-        }
-        return ORB_OK;
-    }
-    int back() {
-        char* b = g_lm.io.as<char>();
-        for (Item& it : items)   // (the first copy synchronises with the null stream)
-            if (it.out) ORB_HIP_TRY(hipMemcpy(it.host, b + it.at, it.bytes, hipMemcpyDeviceToHost));
-        return ORB_OK;
-    }
-};
+thread_local Scratch g_lm;
 
 }  // namespace orbamd
 
@@ -390,7 +349,7 @@ static int lm_host_check(const orblm_batch* b, long long n) {
     return ORB_OK;
 }
 
-static void lm_mirror_batch(LmMirror& m, orblm_batch& d, long long n) {
+static void lm_mirror_batch(Mirror& m, orblm_batch& d, long long n) {
     const size_t s1 = (size_t)d.n_frames1 * d.cap1, s2 = (size_t)d.n_frames2 * d.cap2;
     m.add(d.kps1, s1, true, false); m.add(d.counts1, d.n_frames1, true, false);
     m.add(d.uright1, s1, true, false); m.add(d.depth1, s1, true, false);
@@ -402,12 +361,12 @@ static void lm_mirror_batch(LmMirror& m, orblm_batch& d, long long n) {
     m.add(d.frame1, n, true, false); m.add(d.frame2, n, true, false);
 }
 
-static void lm_mirror_pairs(LmMirror& m, orblm_pairs& q, long long n, bool in) {
+static void lm_mirror_pairs(Mirror& m, orblm_pairs& q, long long n, bool in) {
     m.add(q.F12, 9 * n, in, !in); m.add(q.ep2, 2 * n, in, !in); m.add(q.baseline, n, in, !in); m.add(q.median, n, in, !in);
     m.add(q.skip, n, in, !in); m.add(q.frame1, n, in, !in); m.add(q.frame2, n, in, !in); m.add(q.consts, 64 * n, in, !in);
 }
 
-static void lm_mirror_points(LmMirror& m, orblm_points& o, const orblm_batch& b, long long n) {
+static void lm_mirror_points(Mirror& m, orblm_points& o, const orblm_batch& b, long long n) {
     const size_t c = (size_t)n * b.cap1;
     m.add(o.status, c, true, true); m.add(o.branch, c, true, true); m.add(o.xw, 3 * c, true, true); m.add(o.normal, 3 * c, true, true);
     m.add(o.min_distance, c, true, true); m.add(o.max_distance, c, true, true);
@@ -421,16 +380,12 @@ extern "C" int orblm_prepare_pairs(const orblm_batch* b, const orblm_pairs* pair
     if ((rc = lm_common(b, pairs, n, a))) return rc;
     if (n == 0) return ORB_OK;
     if ((rc = lm_host_check(b, n))) return rc;
-    ORB_HIP_TRY(hipSetDevice(device));
-    g_lm.use_device(device);
     orblm_batch d = *b;
     orblm_pairs q = *pairs;
-    LmMirror m;
+    Mirror m;
     lm_mirror_batch(m, d, n);
     lm_mirror_pairs(m, q, n, false);
-    if ((rc = m.go())) return rc;
-    if ((rc = orblm_prepare_pairs_device(&d, &q, nullptr))) return rc;
-    return m.back();
+    return run_host(g_lm, device, m, [&] { return orblm_prepare_pairs_device(&d, &q, nullptr); });
 }
 
 extern "C" int orblm_triangulate(const orblm_batch* b, const orblm_pairs* pairs, const int32_t* match12,
@@ -448,24 +403,18 @@ extern "C" int orblm_triangulate(const orblm_batch* b, const orblm_pairs* pairs,
         ORB_CHECK_ARG(pairs->frame1[p] >= 0 && pairs->frame1[p] < b->n_frames1 && pairs->frame2[p] >= 0 &&
                           pairs->frame2[p] < b->n_frames2, "pairs name a keyframe that is not there");
     }
-    ORB_HIP_TRY(hipSetDevice(device));
-    g_lm.use_device(device);
     orblm_batch d = *b;
     orblm_pairs q = *pairs;
     orblm_points o = *out;
     const int32_t* dm = match12;
-    LmMirror m;
+    Mirror m;
     lm_mirror_batch(m, d, n);
     lm_mirror_pairs(m, q, n, true);
     lm_mirror_points(m, o, d, n);
     m.add(dm, (size_t)n * b->cap1, true, false);
     m.add(o.has_mappoint1, (size_t)b->n_frames1 * b->cap1, true, true);
-    if (out->has_mappoint2 && (const void*)out->has_mappoint2 != (const void*)out->has_mappoint1)
-        m.add(o.has_mappoint2, (size_t)b->n_frames2 * b->cap2, true, true);
-    if ((rc = m.go())) return rc;
-    if (out->has_mappoint2 && (const void*)out->has_mappoint2 == (const void*)out->has_mappoint1) o.has_mappoint2 = o.has_mappoint1;
-    if ((rc = orblm_triangulate_device(&d, &q, dm, &o, nullptr))) return rc;
-    return m.back();
+    m.add(o.has_mappoint2, (size_t)b->n_frames2 * b->cap2, true, true, true);   // may be has_mappoint1
+    return run_host(g_lm, device, m, [&] { return orblm_triangulate_device(&d, &q, dm, &o, nullptr); });
 }
 
 extern "C" int orblm_create_new_map_points(const orblm_batch* b, const orbm_tri_batch* search, int32_t n_rounds,
@@ -499,14 +448,12 @@ extern "C" int orblm_create_new_map_points(const orblm_batch* b, const orbm_tri_
             for (int f = 0; f < std::min(b->n_frames1, b->n_frames2); f++)
                 ORB_CHECK_ARG(!(seen1[f] && seen2[f]), "a round names a keyframe as keyframe 1 and as keyframe 2");
     }
-    ORB_HIP_TRY(hipSetDevice(device));
-    g_lm.use_device(device);
     orblm_batch d = *b;
     orbm_tri_batch s = *search;
     orblm_pairs q = *pairs;
     orblm_points o = *out;
     int32_t *dm = match12, *dn = nmatches;
-    LmMirror m;
+    Mirror m;
     lm_mirror_batch(m, d, n);
     lm_mirror_pairs(m, q, n, false);
     lm_mirror_points(m, o, d, n);
@@ -515,9 +462,6 @@ extern "C" int orblm_create_new_map_points(const orblm_batch* b, const orbm_tri_
     m.add(dm, (size_t)n * b->cap1, true, true);
     m.add(dn, n, true, true);
     m.add(o.has_mappoint1, (size_t)b->n_frames1 * b->cap1, true, true);
-    if (!same) m.add(o.has_mappoint2, (size_t)b->n_frames2 * b->cap2, true, true);
-    if ((rc = m.go())) return rc;
-    if (same) o.has_mappoint2 = o.has_mappoint1;
-    if ((rc = orblm_create_new_map_points_device(&d, &s, n_rounds, &q, &o, dm, dn, nullptr))) return rc;
-    return m.back();
+    m.add(o.has_mappoint2, (size_t)b->n_frames2 * b->cap2, true, true, true);   // one array when they are the same
+    return run_host(g_lm, device, m, [&] { return orblm_create_new_map_points_device(&d, &s, n_rounds, &q, &o, dm, dn, nullptr); });
 }

@@ -20,7 +20,9 @@
 //                             for EraseObservation, one wavefront per neighbour for EraseConnection, one for the tree
 //   mm_compact_*_kernel       the observation CSR without erased entries: count per point, one scan, fill
 // The observation edits (MapPoint::AddObservation / Replace and the loops that call them; the rules are
-// csrc/mm_observe.h's) are orbmm_observe.inc, included at the end.
+// csrc/mm_observe.h's) are orbmm_observe.hip.  The lane groups and the scan both units launch with are
+// csrc/mm_groups.h's, the per-thread buffers and the shared table checks csrc/mm_host.h's; the host entries stage with
+// common.h's Mirror and run_host.
 #include <algorithm>
 #include <cstdlib>
 #include <vector>
@@ -28,38 +30,14 @@
 #include "common.h"
 #include "mm_connect.h"
 #include "mm_cull.h"
+#include "mm_groups.h"
+#include "mm_host.h"
 #include "mm_normal.h"
 
 namespace orbamd {
 
 constexpr int MM_WINDOW_MAX = 8192, MM_WINDOW_MIN = 64;   // int32 counters in LDS: 32 KiB at most
 constexpr int MM_TILE = 1024;
-
-struct MmWave {
-    int lane;
-    static constexpr int width = 64;
-    __device__ void sync() const { __syncthreads(); }   // one wavefront per workgroup: a wait and a fence
-    __device__ int sum(int v) const {
-#pragma unroll
-        for (int s = 32; s > 0; s >>= 1) v += __shfl_xor(v, s, 64);
-        return v;
-    }
-    __device__ int min(int v) const {
-#pragma unroll
-        for (int s = 32; s > 0; s >>= 1) v = ::min(v, __shfl_xor(v, s, 64));
-        return v;
-    }
-    __device__ int max(int v) const {
-#pragma unroll
-        for (int s = 32; s > 0; s >>= 1) v = ::max(v, __shfl_xor(v, s, 64));
-        return v;
-    }
-    __device__ int prefix(bool flag, int& total) const {
-        const unsigned long long b = __ballot(flag);
-        total = __popcll(b);
-        return __popcll(b & ((1ull << lane) - 1));
-    }
-};
 
 __global__ __launch_bounds__(256) void mm_center_kernel(const float* kf_pose, float* kf_ow, int K) {
     const int k = blockIdx.x * 256 + threadIdx.x;
@@ -114,33 +92,6 @@ __global__ __launch_bounds__(64) void mm_target_kernel(MmGraph t, int B, const M
     mm_commit(g, t, X, items, ws, ww, r);
 }
 
-// Exclusive scan of count[0 .. n) by one workgroup of 256, in place allowed (every entry is read and written by one
-// thread); off[n] = the total.
-__device__ void mm_block_scan(const int32_t* count, int n, int32_t* off, int lo, int hi, int add) {
-    __shared__ int s_wave[4];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    int carry = 0;
-    for (int base = 0; base < n; base += 256) {   // uniform trip count
-        const int i = base + (int)threadIdx.x;
-        const int v = i < n ? ::min(::max(count[i], lo), hi) + add : 0;
-        int x = v;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const int y = __shfl_up(x, d, 64);
-            if (lane >= d) x += y;
-        }
-        if (lane == 63) s_wave[wave] = x;
-        __syncthreads();
-        int before = 0;
-        for (int q = 0; q < wave; q++) before += s_wave[q];
-        const int total = (s_wave[0] + s_wave[1]) + (s_wave[2] + s_wave[3]);
-        if (i < n) off[i] = carry + before + x - v;
-        carry += total;
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) off[n] = carry;
-}
-
 // bad (may be NULL): keyframes that are nobody's child
 __global__ __launch_bounds__(256) void mm_children_kernel(int K, const int32_t* parent, const uint8_t* bad, int32_t* off,
                                                           int32_t* idx) {
@@ -160,7 +111,7 @@ __global__ __launch_bounds__(256) void mm_children_kernel(int K, const int32_t* 
         if (p < K) off[p] = c;
     }
     __syncthreads();
-    mm_block_scan(off, K, off, 0, K, 0);
+    mm_block_scan<int32_t>(off, K, off, 0, K, 0);
     __syncthreads();
     // fill: k ascending per parent; the lists hold K entries at most in all
     for (int pb = 0; pb < K; pb += 256) {
@@ -182,7 +133,7 @@ __global__ __launch_bounds__(256) void mm_children_kernel(int K, const int32_t* 
 // query outside the table has an empty list)
 __global__ __launch_bounds__(256) void mm_offsets_kernel(MmGraph t, orbmm_csr o, int mode, int32_t* q_count) {
     if (mode == 0) {
-        mm_block_scan(t.n_ord, t.K, o.covis_begin, 0, t.conn_cap, 0);
+        mm_block_scan<int32_t>(t.n_ord, t.K, o.covis_begin, 0, t.conn_cap, 0);
         return;
     }
     for (int q = threadIdx.x; q < o.n_queries; q += 256) {
@@ -190,7 +141,7 @@ __global__ __launch_bounds__(256) void mm_offsets_kernel(MmGraph t, orbmm_csr o,
         q_count[q] = (k >= 0 && k < t.K) ? mm_clamp(t.n_conn[k], 0, t.conn_cap) + (o.append_self ? 1 : 0) : 0;
     }
     __syncthreads();
-    mm_block_scan(q_count, o.n_queries, o.conn_off, 0, t.conn_cap + 1, 0);
+    mm_block_scan<int32_t>(q_count, o.n_queries, o.conn_off, 0, t.conn_cap + 1, 0);
 }
 
 __global__ __launch_bounds__(256) void mm_pack_kernel(MmGraph t, orbmm_csr o, int mode) {
@@ -214,52 +165,6 @@ __global__ __launch_bounds__(256) void mm_pack_kernel(MmGraph t, orbmm_csr o, in
 }
 
 // ---------------------------------------------------------------------------------------------- the culls
-constexpr int MM_CULL_WAVES = 4;
-
-// One wavefront of a workgroup of several: its lanes run in lockstep, so sync() only has to order its memory operations.
-struct MmSubWave : MmWave {
-    __device__ void sync() const {
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
-        __builtin_amdgcn_wave_barrier();
-    }
-};
-
-// The workgroup of MM_CULL_WAVES wavefronts; s: MM_CULL_WAVES ints of LDS.
-struct MmBlock {
-    int lane;
-    int32_t* s;
-    static constexpr int width = 64 * MM_CULL_WAVES;
-    __device__ void sync() const { __syncthreads(); }
-    template <class Op>
-    __device__ int across(int v, Op op) const {   // v: this wavefront's value
-        if ((lane & 63) == 0) s[lane >> 6] = v;
-        __syncthreads();
-        int r = s[0];
-#pragma unroll
-        for (int q = 1; q < MM_CULL_WAVES; q++) r = op(r, s[q]);
-        __syncthreads();
-        return r;
-    }
-    __device__ int sum(int v) const { return across(MmWave{lane & 63}.sum(v), [](int a, int b) { return a + b; }); }
-    __device__ int min(int v) const { return across(MmWave{lane & 63}.min(v), [](int a, int b) { return ::min(a, b); }); }
-    __device__ int max(int v) const { return across(MmWave{lane & 63}.max(v), [](int a, int b) { return ::max(a, b); }); }
-    __device__ int prefix(bool flag, int& total) const {
-        int mine;
-        const int off = MmWave{lane & 63}.prefix(flag, mine);
-        if ((lane & 63) == 0) s[lane >> 6] = mine;
-        __syncthreads();
-        int before = 0;
-        total = 0;
-#pragma unroll
-        for (int q = 0; q < MM_CULL_WAVES; q++) {
-            before += q < (lane >> 6) ? s[q] : 0;
-            total += s[q];
-        }
-        __syncthreads();
-        return before + off;
-    }
-};
-
 __global__ __launch_bounds__(256) void mm_cull_points_kernel(MmCull t, const int32_t* recent, int n, int cur_kf_id, int min_obs,
                                                              uint8_t* keep) {
     const int i = blockIdx.x * 256 + threadIdx.x;
@@ -305,7 +210,7 @@ __global__ __launch_bounds__(256) void mm_compact_count_kernel(int M, int n_obs,
 }
 
 __global__ __launch_bounds__(256) void mm_compact_scan_kernel(int M, int n_obs, int32_t* out_off) {
-    mm_block_scan(out_off, M, out_off, 0, n_obs, 0);
+    mm_block_scan<int32_t>(out_off, M, out_off, 0, n_obs, 0);
 }
 
 __global__ __launch_bounds__(256) void mm_compact_fill_kernel(int M, int n_obs, const int32_t* off, const int32_t* kf,
@@ -315,71 +220,11 @@ __global__ __launch_bounds__(256) void mm_compact_fill_kernel(int M, int n_obs, 
     if (p < M) cull_compact_point(n_obs, off, kf, idx, p, out_off[p], out_kf, out_idx);
 }
 
-struct MmScratch {
-    DevBuf ws, io;
-    int device = -1;
-    void use_device(int dev) {
-        if (device != dev) {
-            ws.release();
-            io.release();
-            device = dev;
-        }
-    }
-};
-
 }  // namespace orbamd
 
 using namespace orbamd;
 
 namespace {
-
-thread_local MmScratch g_mm;
-
-constexpr long long MM_MAX_ENTRIES = 0x7fffffffLL;
-
-struct MmStage {   // bump allocation: measure, then place
-    size_t o = 0;
-    size_t take(size_t bytes) { const size_t r = o; o += align_up(std::max<size_t>(bytes, 1), 256); return r; }
-};
-
-// Host staging of one call: inputs copied in, the updated arrays copied back.
-struct MmIo {
-    struct Item { const void* host; size_t bytes; void** dev; bool in, out; size_t at; };
-    std::vector<Item> items;
-    template <class T>
-    void add(T*& field, size_t count, bool in, bool out) {
-        if (field) items.push_back({field, count * sizeof(*field), (void**)&field, in, out, 0});
-    }
-    int upload(DevBuf& buf) {
-        MmStage s;
-        for (Item& i : items) i.at = s.take(i.bytes);
-        int rc;
-        if ((rc = buf.reserve(s.o))) return rc;
-        char* d = buf.as<char>();
-        for (Item& i : items) {
-            if (i.in && i.bytes) ORB_HIP_TRY(hipMemcpy(d + i.at, i.host, i.bytes, hipMemcpyHostToDevice));
-            *i.dev = d + i.at;
-        }
-        return ORB_OK;
-    }
-    int download() {
-        for (Item& i : items)
-            if (i.out && i.bytes) ORB_HIP_TRY(hipMemcpy((void*)i.host, *i.dev, i.bytes, hipMemcpyDeviceToHost));
-        return ORB_OK;
-    }
-};
-
-int mm_check_csr(const int32_t* off, int n, int n_obs, const char* what) {
-    ORB_CHECK_ARG(off[0] == 0, std::string(what) + ": offsets must start at 0");
-    for (int i = 0; i < n; i++) ORB_CHECK_ARG(off[i + 1] >= off[i], std::string(what) + ": offsets must not decrease");
-    ORB_CHECK_ARG(off[n] <= n_obs, std::string(what) + ": offsets end past n_obs");
-    return ORB_OK;
-}
-
-int mm_check_range(const int32_t* a, size_t n, int lo, int hi, const char* msg) {
-    for (size_t i = 0; i < n; i++) ORB_CHECK_ARG(a[i] >= lo && a[i] < hi, msg);
-    return ORB_OK;
-}
 
 int mm_points_check(const orbmm_points* p) {
     ORB_CHECK_ARG(p, "null points");
@@ -400,17 +245,17 @@ int mm_points_check(const orbmm_points* p) {
 int mm_points_check_host(const orbmm_points* p) {
     const int K = p->n_keyframes, M = p->n_mappoints;
     int rc;
-    if ((rc = mm_check_csr(p->mp_obs_off, M, p->n_obs, "mp_obs"))) return rc;
+    if ((rc = check_csr(p->mp_obs_off, M, p->n_obs, "mp_obs"))) return rc;
     const size_t n_obs = p->mp_obs_off[M];
-    if ((rc = mm_check_range(p->mp_obs_kf, n_obs, 0, K, "mp_obs_kf entry outside [0, n_keyframes)"))) return rc;
-    if ((rc = mm_check_range(p->mp_obs_idx, n_obs, 0, p->kf_cap, "mp_obs_idx entry outside [0, kf_cap)"))) return rc;
-    if ((rc = mm_check_range(p->mp_ref_kf, M, -1, K, "mp_ref_kf outside [-1, n_keyframes)"))) return rc;
-    if ((rc = mm_check_range(p->kf_n, K, 0, p->kf_cap + 1, "kf_n outside [0, kf_cap]"))) return rc;
+    if ((rc = check_range(p->mp_obs_kf, n_obs, 0, K, "mp_obs_kf entry outside [0, n_keyframes)"))) return rc;
+    if ((rc = check_range(p->mp_obs_idx, n_obs, 0, p->kf_cap, "mp_obs_idx entry outside [0, kf_cap)"))) return rc;
+    if ((rc = check_range(p->mp_ref_kf, M, -1, K, "mp_ref_kf outside [-1, n_keyframes)"))) return rc;
+    if ((rc = check_range(p->kf_n, K, 0, p->kf_cap + 1, "kf_n outside [0, kf_cap]"))) return rc;
     for (int k = 0; k < K; k++)
-        if ((rc = mm_check_range(p->kf_kp_octave + (size_t)k * p->kf_cap, p->kf_n[k], 0, p->n_levels,
+        if ((rc = check_range(p->kf_kp_octave + (size_t)k * p->kf_cap, p->kf_n[k], 0, p->n_levels,
                                  "kf_kp_octave entry outside [0, n_levels)")))
             return rc;
-    if (p->point && (rc = mm_check_range(p->point, p->n_points, 0, M, "point outside [0, n_mappoints)"))) return rc;
+    if (p->point && (rc = check_range(p->point, p->n_points, 0, M, "point outside [0, n_mappoints)"))) return rc;
     return ORB_OK;
 }
 
@@ -437,29 +282,21 @@ int mm_items_check(const orbmm_graph* g, int32_t n_items, const int32_t* item) {
     return ORB_OK;
 }
 
-int mm_rows_check_host(const orbmm_graph* g) {
-    const int K = g->n_keyframes, cap = g->conn_cap;
-    for (int k = 0; k < K; k++) {
-        ORB_CHECK_ARG(g->n_conn[k] >= 0 && g->n_conn[k] <= cap, "n_conn outside [0, conn_cap]");
-        ORB_CHECK_ARG(g->n_ord[k] >= 0 && g->n_ord[k] <= cap, "n_ord outside [0, conn_cap]");
-        int rc;
-        if ((rc = mm_check_range(g->conn_slot + (size_t)k * cap, g->n_conn[k], 0, K, "conn_slot entry outside [0, n_keyframes)"))) return rc;
-        if ((rc = mm_check_range(g->ord_slot + (size_t)k * cap, g->n_ord[k], 0, K, "ord_slot entry outside [0, n_keyframes)"))) return rc;
-    }
-    return ORB_OK;
+int mm_graph_rows_check_host(const orbmm_graph* g) {
+    return mm_rows_check_host(g->n_keyframes, g->conn_cap, g->conn_slot, g->n_conn, g->ord_slot, g->n_ord);
 }
 
 int mm_graph_check_host(const orbmm_graph* g, int32_t n_items, const int32_t* item) {
     const int K = g->n_keyframes, M = g->n_mappoints;
     int rc;
-    if ((rc = mm_check_range(g->kf_n, K, 0, g->kf_cap + 1, "kf_n outside [0, kf_cap]"))) return rc;
-    if ((rc = mm_check_range(g->kf_mappoint, (size_t)K * g->kf_cap, -1, M, "kf_mappoint entry outside [-1, n_mappoints)"))) return rc;
-    if ((rc = mm_check_csr(g->mp_obs_off, M, g->n_obs, "mp_obs"))) return rc;
-    if ((rc = mm_check_range(g->mp_obs_kf, g->mp_obs_off[M], 0, K, "mp_obs_kf entry outside [0, n_keyframes)"))) return rc;
-    if ((rc = mm_rows_check_host(g))) return rc;
-    if ((rc = mm_check_range(g->kf_parent, K, -1, K, "kf_parent outside [-1, n_keyframes)"))) return rc;
-    if ((rc = mm_check_range(g->kf_covis, (size_t)K * MM_COVIS, -1, K, "kf_covis entry outside [-1, n_keyframes)"))) return rc;
-    return mm_check_range(item, n_items, 0, K, "item outside [0, n_keyframes)");
+    if ((rc = check_range(g->kf_n, K, 0, g->kf_cap + 1, "kf_n outside [0, kf_cap]"))) return rc;
+    if ((rc = check_range(g->kf_mappoint, (size_t)K * g->kf_cap, -1, M, "kf_mappoint entry outside [-1, n_mappoints)"))) return rc;
+    if ((rc = check_csr(g->mp_obs_off, M, g->n_obs, "mp_obs"))) return rc;
+    if ((rc = check_range(g->mp_obs_kf, g->mp_obs_off[M], 0, K, "mp_obs_kf entry outside [0, n_keyframes)"))) return rc;
+    if ((rc = mm_graph_rows_check_host(g))) return rc;
+    if ((rc = check_range(g->kf_parent, K, -1, K, "kf_parent outside [-1, n_keyframes)"))) return rc;
+    if ((rc = check_range(g->kf_covis, (size_t)K * MM_COVIS, -1, K, "kf_covis entry outside [-1, n_keyframes)"))) return rc;
+    return check_range(item, n_items, 0, K, "item outside [0, n_keyframes)");
 }
 
 MmGraph mm_graph(const orbmm_graph& g) {
@@ -486,13 +323,6 @@ int mm_window() {   // read per call
     int w = MM_WINDOW_MAX;
     if (const char* e = getenv("ORBMM_WINDOW")) w = atoi(e);
     return std::max(MM_WINDOW_MIN, std::min(MM_WINDOW_MAX, w));
-}
-
-int mm_use_current_device() {
-    int dev = 0;
-    ORB_HIP_TRY(hipGetDevice(&dev));
-    g_mm.use_device(dev);
-    return ORB_OK;
 }
 
 }  // namespace
@@ -526,30 +356,67 @@ extern "C" int orbmm_update_connections_device(const orbmm_graph* g, int32_t n_i
     hipStream_t st = (hipStream_t)stream;
     const MmGraph t = mm_graph(*g);
     const size_t K = t.K, B = n_items;
-    MmStage s;   // the counters, the item summaries, the working rows
-    const size_t o_cnt = s.take(B * K * 4), o_items = s.take(B * sizeof(MmItem)), o_work = s.take(2 * K * t.conn_cap * 4);
-    if ((rc = g_mm.ws.reserve(s.o))) return rc;
-    char* w = g_mm.ws.as<char>();
-    int32_t* cnt = (int32_t*)(w + o_cnt);
-    MmItem* items = (MmItem*)(w + o_items);
+    int32_t *cnt, *work;   // the counters, the item summaries, the working rows
+    MmItem* items;
+    auto carve = [&](char* base) {
+        Carver c{base};
+        c.take(cnt, B * K); c.take(items, B); c.take(work, 2 * K * t.conn_cap);
+        return c.off;
+    };
+    if ((rc = g_mm.ws.reserve(carve(nullptr)))) return rc;
+    carve(g_mm.ws.as<char>());
     if (B) {
         const int window = std::min(mm_window(), std::max((int)K, MM_WINDOW_MIN));
         hipLaunchKernelGGL(mm_count_kernel, dim3((unsigned)B), dim3(256), (size_t)window * 4, st, t, item, cnt, window);
         hipLaunchKernelGGL(mm_item_kernel, dim3((unsigned)B), dim3(64), 0, st, item, cnt, items, (int)K);
     }
-    hipLaunchKernelGGL(mm_target_kernel, dim3((unsigned)K), dim3(64), 0, st, t, (int)B, items, cnt, (int32_t*)(w + o_work));
+    hipLaunchKernelGGL(mm_target_kernel, dim3((unsigned)K), dim3(64), 0, st, t, (int)B, items, cnt, work);
     ORB_HIP_TRY(hipGetLastError());
     return ORB_OK;
 }
 
-extern "C" int orbmm_children_device(int32_t n_keyframes, const int32_t* kf_parent, int32_t* kf_child_off,
-                                     int32_t* kf_child_idx, void* stream) {
+namespace {
+
+// kf_bad (may be NULL): keyframes that are nobody's child
+int mm_children_device(int32_t n_keyframes, const int32_t* kf_parent, const uint8_t* kf_bad, bool need_bad, int32_t* kf_child_off,
+                       int32_t* kf_child_idx, void* stream) {
     ORB_CHECK_ARG(n_keyframes >= 0, "negative sizes");
-    ORB_CHECK_ARG(kf_child_off && (n_keyframes == 0 || (kf_parent && kf_child_idx)), "null children array");
-    hipLaunchKernelGGL(mm_children_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, n_keyframes, kf_parent,
-                       (const uint8_t*)nullptr, kf_child_off, kf_child_idx);
+    ORB_CHECK_ARG(kf_child_off && (n_keyframes == 0 || (kf_parent && (kf_bad || !need_bad) && kf_child_idx)), "null children array");
+    hipLaunchKernelGGL(mm_children_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, n_keyframes, kf_parent, kf_bad,
+                       kf_child_off, kf_child_idx);
     ORB_HIP_TRY(hipGetLastError());
     return ORB_OK;
+}
+
+int mm_children(int32_t n_keyframes, const int32_t* kf_parent, const uint8_t* kf_bad, bool need_bad, int32_t* kf_child_off,
+                int32_t* kf_child_idx, int device) {
+    ORB_CHECK_ARG(n_keyframes >= 0, "negative sizes");
+    ORB_CHECK_ARG(kf_child_off && (n_keyframes == 0 || (kf_parent && (kf_bad || !need_bad) && kf_child_idx)), "null children array");
+    int rc;
+    if ((rc = check_range(kf_parent, n_keyframes, -1, n_keyframes, "kf_parent outside [-1, n_keyframes)"))) return rc;
+    if (n_keyframes == 0) {
+        kf_child_off[0] = 0;
+        return ORB_OK;
+    }
+    const size_t K = n_keyframes;
+    Mirror io;
+    io.add(kf_parent, K, true, false); io.add(kf_bad, K, true, false); io.add(kf_child_off, K + 1, false, true);
+    io.add(kf_child_idx, K, true, true);
+    return run_host(g_mm, device, io, [&] {
+        return mm_children_device(n_keyframes, kf_parent, kf_bad, need_bad, kf_child_off, kf_child_idx, nullptr);
+    });
+}
+
+}  // namespace
+
+extern "C" int orbmm_children_device(int32_t n_keyframes, const int32_t* kf_parent, int32_t* kf_child_off,
+                                     int32_t* kf_child_idx, void* stream) {
+    return mm_children_device(n_keyframes, kf_parent, nullptr, false, kf_child_off, kf_child_idx, stream);
+}
+
+extern "C" int orbmm_children_live_device(int32_t n_keyframes, const int32_t* kf_parent, const uint8_t* kf_bad,
+                                          int32_t* kf_child_off, int32_t* kf_child_idx, void* stream) {
+    return mm_children_device(n_keyframes, kf_parent, kf_bad, true, kf_child_off, kf_child_idx, stream);
 }
 
 extern "C" int orbmm_covis_csr_device(const orbmm_graph* g, const orbmm_csr* out, void* stream) {
@@ -565,8 +432,8 @@ extern "C" int orbmm_covis_csr_device(const orbmm_graph* g, const orbmm_csr* out
         if (t.K) hipLaunchKernelGGL(mm_pack_kernel, dim3((unsigned)t.K, cols), dim3(256), 0, st, t, *out, 0);
     }
     if (conn) {
-        if ((rc = g_mm.io.reserve(std::max<size_t>((size_t)out->n_queries * 4, 256)))) return rc;
-        hipLaunchKernelGGL(mm_offsets_kernel, dim3(1), dim3(256), 0, st, t, *out, 1, g_mm.io.as<int32_t>());
+        if ((rc = g_mm.ws.reserve(std::max<size_t>((size_t)out->n_queries * 4, 256)))) return rc;
+        hipLaunchKernelGGL(mm_offsets_kernel, dim3(1), dim3(256), 0, st, t, *out, 1, g_mm.ws.as<int32_t>());
         if (out->n_queries) hipLaunchKernelGGL(mm_pack_kernel, dim3((unsigned)out->n_queries, cols), dim3(256), 0, st, t, *out, 1);
     }
     ORB_HIP_TRY(hipGetLastError());
@@ -579,25 +446,20 @@ extern "C" int orbmm_update_normal_depth(const orbmm_points* p, int device) {
     const int n = p->point ? p->n_points : p->n_mappoints;
     if (n == 0 || p->n_keyframes == 0) return ORB_OK;
     if ((rc = mm_points_check_host(p))) return rc;   // before any copy
-    ORB_HIP_TRY(hipSetDevice(device));
-    g_mm.use_device(device);
     const size_t K = p->n_keyframes, M = p->n_mappoints, n_obs = p->mp_obs_off[M];
     orbmm_points d = *p;
-    MmIo io;
+    Mirror io;
     io.add(d.mp_bad, M, true, false); io.add(d.mp_xw, M * 3, true, false); io.add(d.mp_ref_kf, M, true, false);
     io.add(d.mp_obs_off, M + 1, true, false); io.add(d.mp_obs_kf, n_obs, true, false); io.add(d.mp_obs_idx, n_obs, true, false);
     io.add(d.kf_pose, K * 12, true, false); io.add(d.kf_n, K, true, false); io.add(d.kf_kp_octave, K * p->kf_cap, true, false);
     io.add(d.point, (size_t)p->n_points, true, false);
     io.add(d.mp_normal, M * 3, true, true); io.add(d.mp_max_min, M * 2, true, true);
-    if ((rc = io.upload(g_mm.io))) return rc;
-    if ((rc = orbmm_update_normal_depth_device(&d, nullptr))) return rc;
-    ORB_HIP_TRY(hipStreamSynchronize(nullptr));
-    return io.download();
+    return run_host(g_mm, device, io, [&] { return orbmm_update_normal_depth_device(&d, nullptr); });
 }
 
 namespace {
 
-void mm_add_rows(MmIo& io, orbmm_graph& d, bool out) {
+void mm_add_rows(Mirror& io, orbmm_graph& d, bool out) {
     const size_t K = d.n_keyframes, rows = K * d.conn_cap;
     io.add(d.conn_slot, rows, true, out); io.add(d.conn_weight, rows, true, out); io.add(d.n_conn, K, true, out);
     io.add(d.ord_slot, rows, true, out); io.add(d.ord_weight, rows, true, out); io.add(d.n_ord, K, true, out);
@@ -611,12 +473,10 @@ extern "C" int orbmm_update_connections(const orbmm_graph* g, int32_t n_items, c
     if ((rc = mm_items_check(g, n_items, item))) return rc;
     if (g->n_keyframes == 0) return ORB_OK;
     if ((rc = mm_graph_check_host(g, n_items, item))) return rc;   // before any copy
-    ORB_HIP_TRY(hipSetDevice(device));
-    g_mm.use_device(device);
     const size_t K = g->n_keyframes, M = g->n_mappoints;
     orbmm_graph d = *g;
     const int32_t* d_item = item;
-    MmIo io;
+    Mirror io;
     io.add(d.kf_id, K, true, false); io.add(d.kf_n, K, true, false); io.add(d.kf_mappoint, K * g->kf_cap, true, false);
     io.add(d.mp_bad, M, true, false); io.add(d.mp_obs_off, M + 1, true, false);
     io.add(d.mp_obs_kf, (size_t)g->mp_obs_off[M], true, false);
@@ -624,44 +484,29 @@ extern "C" int orbmm_update_connections(const orbmm_graph* g, int32_t n_items, c
     io.add(d.kf_first_connection, K, true, true); io.add(d.kf_parent, K, true, true); io.add(d.kf_covis, K * MM_COVIS, true, true);
     io.add(d.status, K, false, true);
     io.add(d_item, (size_t)n_items, true, false);
-    if ((rc = io.upload(g_mm.io))) return rc;
-    if ((rc = orbmm_update_connections_device(&d, n_items, d_item, nullptr))) return rc;
-    ORB_HIP_TRY(hipStreamSynchronize(nullptr));
-    return io.download();
+    return run_host(g_mm, device, io, [&] { return orbmm_update_connections_device(&d, n_items, d_item, nullptr); });
 }
 
 extern "C" int orbmm_children(int32_t n_keyframes, const int32_t* kf_parent, int32_t* kf_child_off, int32_t* kf_child_idx,
                               int device) {
-    ORB_CHECK_ARG(n_keyframes >= 0, "negative sizes");
-    ORB_CHECK_ARG(kf_child_off && (n_keyframes == 0 || (kf_parent && kf_child_idx)), "null children array");
-    int rc;
-    if ((rc = mm_check_range(kf_parent, n_keyframes, -1, n_keyframes, "kf_parent outside [-1, n_keyframes)"))) return rc;
-    if (n_keyframes == 0) {
-        kf_child_off[0] = 0;
-        return ORB_OK;
-    }
-    ORB_HIP_TRY(hipSetDevice(device));
-    g_mm.use_device(device);
-    const size_t K = n_keyframes;
-    MmIo io;
-    io.add(kf_parent, K, true, false); io.add(kf_child_off, K + 1, false, true); io.add(kf_child_idx, K, true, true);
-    if ((rc = io.upload(g_mm.io))) return rc;
-    if ((rc = orbmm_children_device(n_keyframes, kf_parent, kf_child_off, kf_child_idx, nullptr))) return rc;
-    ORB_HIP_TRY(hipStreamSynchronize(nullptr));
-    return io.download();
+    return mm_children(n_keyframes, kf_parent, nullptr, false, kf_child_off, kf_child_idx, device);
+}
+
+extern "C" int orbmm_children_live(int32_t n_keyframes, const int32_t* kf_parent, const uint8_t* kf_bad, int32_t* kf_child_off,
+                                   int32_t* kf_child_idx, int device) {
+    return mm_children(n_keyframes, kf_parent, kf_bad, true, kf_child_off, kf_child_idx, device);
 }
 
 extern "C" int orbmm_covis_csr(const orbmm_graph* g, const orbmm_csr* out, int device) {
     int rc;
     bool covis = false, conn = false;
     if ((rc = mm_csr_check(g, out, covis, conn))) return rc;
-    if ((rc = mm_rows_check_host(g))) return rc;   // before any copy
-    if (conn && (rc = mm_check_range(out->query, out->n_queries, 0, g->n_keyframes, "query outside [0, n_keyframes)"))) return rc;
-    ORB_HIP_TRY(hipSetDevice(device));
+    if ((rc = mm_graph_rows_check_host(g))) return rc;   // before any copy
+    if (conn && (rc = check_range(out->query, out->n_queries, 0, g->n_keyframes, "query outside [0, n_keyframes)"))) return rc;
     const size_t K = g->n_keyframes, rows = K * g->conn_cap, Q = conn ? out->n_queries : 0;
     orbmm_graph d = *g;
     orbmm_csr o = *out;
-    MmIo io;
+    Mirror io;
     mm_add_rows(io, d, false);
     io.add(o.kf_bad, K, true, false);
     if (covis) {
@@ -672,14 +517,7 @@ extern "C" int orbmm_covis_csr(const orbmm_graph* g, const orbmm_csr* out, int d
         io.add(o.query, Q, true, false); io.add(o.conn_off, Q + 1, false, true);
         io.add(o.conn_idx, Q * (g->conn_cap + 1), true, true);
     }
-    // the device form's query counts live in g_mm.io: stage in a buffer of this call's own
-    DevBuf stage;
-    if ((rc = io.upload(stage))) { stage.release(); return rc; }
-    rc = orbmm_covis_csr_device(&d, &o, nullptr);
-    if (!rc && hipStreamSynchronize(nullptr) != hipSuccess) { set_error("hipStreamSynchronize failed"); rc = ORB_EHIP; }
-    if (!rc) rc = io.download();
-    stage.release();
-    return rc;
+    return run_host(g_mm, device, io, [&] { return orbmm_covis_csr_device(&d, &o, nullptr); });
 }
 
 // ---------------------------------------------------------------------------------------------- the culls: entries
@@ -717,11 +555,11 @@ int mm_cull_check(const orbmm_cull* c, bool keyframes) {
 int mm_cull_check_host(const orbmm_cull* c, bool keyframes) {
     const int K = c->n_keyframes, M = c->n_mappoints;
     int rc;
-    if ((rc = mm_check_csr(c->mp_obs_off, M, c->n_obs, "mp_obs"))) return rc;
+    if ((rc = check_csr(c->mp_obs_off, M, c->n_obs, "mp_obs"))) return rc;
     const size_t n_obs = c->mp_obs_off[M];
-    if ((rc = mm_check_range(c->mp_obs_kf, n_obs, 0, K, "mp_obs_kf entry outside [0, n_keyframes)"))) return rc;
-    if ((rc = mm_check_range(c->mp_obs_idx, n_obs, 0, c->kf_cap, "mp_obs_idx entry outside [0, kf_cap)"))) return rc;
-    if ((rc = mm_check_range(c->kf_mappoint, (size_t)K * c->kf_cap, -1, M, "kf_mappoint entry outside [-1, n_mappoints)"))) return rc;
+    if ((rc = check_range(c->mp_obs_kf, n_obs, 0, K, "mp_obs_kf entry outside [0, n_keyframes)"))) return rc;
+    if ((rc = check_range(c->mp_obs_idx, n_obs, 0, c->kf_cap, "mp_obs_idx entry outside [0, kf_cap)"))) return rc;
+    if ((rc = check_range(c->kf_mappoint, (size_t)K * c->kf_cap, -1, M, "kf_mappoint entry outside [-1, n_mappoints)"))) return rc;
     std::vector<int32_t> seen(K, -1);   // a keyframe twice in a point's observations
     for (int p = 0; p < M; p++)
         for (int e = c->mp_obs_off[p]; e < c->mp_obs_off[p + 1]; e++) {
@@ -729,27 +567,14 @@ int mm_cull_check_host(const orbmm_cull* c, bool keyframes) {
             seen[c->mp_obs_kf[e]] = p;
         }
     if (!keyframes) return ORB_OK;
-    if ((rc = mm_check_range(c->kf_n, K, 0, c->kf_cap + 1, "kf_n outside [0, kf_cap]"))) return rc;
-    seen.assign(M, -1);                 // a point twice in a keyframe's row
-    for (int k = 0; k < K; k++)
-        for (int i = 0; i < c->kf_n[k]; i++) {
-            const int p = c->kf_mappoint[(size_t)k * c->kf_cap + i];
-            if (p < 0) continue;
-            ORB_CHECK_ARG(seen[p] != k, "a map point twice in a keyframe's row");
-            seen[p] = k;
-        }
-    if ((rc = mm_check_range(c->mp_ref_kf, M, -1, K, "mp_ref_kf outside [-1, n_keyframes)"))) return rc;
-    if ((rc = mm_check_range(c->kf_parent, K, -1, K, "kf_parent outside [-1, n_keyframes)"))) return rc;
-    for (int k = 0; k < K; k++) {
-        ORB_CHECK_ARG(c->n_conn[k] >= 0 && c->n_conn[k] <= c->conn_cap, "n_conn outside [0, conn_cap]");
-        ORB_CHECK_ARG(c->n_ord[k] >= 0 && c->n_ord[k] <= c->conn_cap, "n_ord outside [0, conn_cap]");
-        if ((rc = mm_check_range(c->conn_slot + (size_t)k * c->conn_cap, c->n_conn[k], 0, K, "conn_slot entry outside [0, n_keyframes)"))) return rc;
-        if ((rc = mm_check_range(c->ord_slot + (size_t)k * c->conn_cap, c->n_ord[k], 0, K, "ord_slot entry outside [0, n_keyframes)"))) return rc;
-    }
-    return ORB_OK;
+    if ((rc = check_range(c->kf_n, K, 0, c->kf_cap + 1, "kf_n outside [0, kf_cap]"))) return rc;
+    if ((rc = mm_check_rows_distinct(K, M, c->kf_cap, c->kf_n, c->kf_mappoint))) return rc;
+    if ((rc = check_range(c->mp_ref_kf, M, -1, K, "mp_ref_kf outside [-1, n_keyframes)"))) return rc;
+    if ((rc = check_range(c->kf_parent, K, -1, K, "kf_parent outside [-1, n_keyframes)"))) return rc;
+    return mm_rows_check_host(K, c->conn_cap, c->conn_slot, c->n_conn, c->ord_slot, c->n_ord);
 }
 
-void mm_cull_add(MmIo& io, orbmm_cull& d, bool keyframes) {
+void mm_cull_add(Mirror& io, orbmm_cull& d, bool keyframes) {
     const size_t K = d.n_keyframes, M = d.n_mappoints, n_obs = d.mp_obs_off[M], rows = K * (keyframes ? d.conn_cap : 0);
     io.add(d.kf_mappoint, K * d.kf_cap, true, true); io.add(d.mp_bad, M, true, true); io.add(d.mp_nobs, M, true, keyframes);
     io.add(d.mp_obs_kf, n_obs, true, true); io.add(d.mp_obs_idx, n_obs, true, false);
@@ -830,16 +655,6 @@ extern "C" int orbmm_compact_observations_device(int32_t n_mappoints, int32_t n_
     return ORB_OK;
 }
 
-extern "C" int orbmm_children_live_device(int32_t n_keyframes, const int32_t* kf_parent, const uint8_t* kf_bad,
-                                          int32_t* kf_child_off, int32_t* kf_child_idx, void* stream) {
-    ORB_CHECK_ARG(n_keyframes >= 0, "negative sizes");
-    ORB_CHECK_ARG(kf_child_off && (n_keyframes == 0 || (kf_parent && kf_bad && kf_child_idx)), "null children array");
-    hipLaunchKernelGGL(mm_children_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, n_keyframes, kf_parent, kf_bad,
-                       kf_child_off, kf_child_idx);
-    ORB_HIP_TRY(hipGetLastError());
-    return ORB_OK;
-}
-
 extern "C" int orbmm_cull_map_points(const orbmm_cull* c, int32_t n_recent, int32_t* recent, int32_t cur_kf_id,
                                      int32_t monocular, int32_t* n_recent_out, int device) {
     int rc;
@@ -847,17 +662,14 @@ extern "C" int orbmm_cull_map_points(const orbmm_cull* c, int32_t n_recent, int3
     ORB_CHECK_ARG(n_recent >= 0, "negative sizes");
     ORB_CHECK_ARG(n_recent_out && (n_recent == 0 || recent), "null recent list");
     if ((rc = mm_cull_check_host(c, false))) return rc;   // before any copy
-    if ((rc = mm_check_range(recent, n_recent, 0, c->n_mappoints, "recent entry outside [0, n_mappoints)"))) return rc;
-    ORB_HIP_TRY(hipSetDevice(device));
-    g_mm.use_device(device);
+    if ((rc = check_range(recent, n_recent, 0, c->n_mappoints, "recent entry outside [0, n_mappoints)"))) return rc;
     orbmm_cull d = *c;
-    MmIo io;
+    Mirror io;
     mm_cull_add(io, d, false);
     io.add(recent, (size_t)n_recent, true, true); io.add(n_recent_out, 1, false, true);
-    if ((rc = io.upload(g_mm.io))) return rc;
-    if ((rc = orbmm_cull_map_points_device(&d, n_recent, recent, cur_kf_id, monocular, n_recent_out, nullptr))) return rc;
-    ORB_HIP_TRY(hipStreamSynchronize(nullptr));
-    return io.download();
+    return run_host(g_mm, device, io, [&] {
+        return orbmm_cull_map_points_device(&d, n_recent, recent, cur_kf_id, monocular, n_recent_out, nullptr);
+    });
 }
 
 extern "C" int orbmm_cull_keyframes(const orbmm_cull* c, int32_t cur, int32_t monocular, float th_depth, int32_t* culled,
@@ -867,16 +679,13 @@ extern "C" int orbmm_cull_keyframes(const orbmm_cull* c, int32_t cur, int32_t mo
     ORB_CHECK_ARG(culled && n_culled && status, "null output");
     if ((rc = mm_cull_check_host(c, true))) return rc;   // before any copy
     ORB_CHECK_ARG(cur >= 0 && cur < c->n_keyframes, "cur outside [0, n_keyframes)");
-    ORB_HIP_TRY(hipSetDevice(device));
-    g_mm.use_device(device);
     orbmm_cull d = *c;
-    MmIo io;
+    Mirror io;
     mm_cull_add(io, d, true);
     io.add(culled, (size_t)c->conn_cap, false, true); io.add(n_culled, 1, false, true); io.add(status, 1, false, true);
-    if ((rc = io.upload(g_mm.io))) return rc;
-    if ((rc = orbmm_cull_keyframes_device(&d, cur, monocular, th_depth, culled, n_culled, status, nullptr))) return rc;
-    ORB_HIP_TRY(hipStreamSynchronize(nullptr));
-    return io.download();
+    return run_host(g_mm, device, io, [&] {
+        return orbmm_cull_keyframes_device(&d, cur, monocular, th_depth, culled, n_culled, status, nullptr);
+    });
 }
 
 extern "C" int orbmm_compact_observations(int32_t n_mappoints, int32_t n_obs, const int32_t* mp_obs_off, const int32_t* mp_obs_kf,
@@ -884,41 +693,13 @@ extern "C" int orbmm_compact_observations(int32_t n_mappoints, int32_t n_obs, co
                                           int device) {
     int rc;
     if ((rc = mm_compact_check(n_mappoints, n_obs, mp_obs_off, mp_obs_kf, mp_obs_idx, out_off, out_kf, out_idx))) return rc;
-    if ((rc = mm_check_csr(mp_obs_off, n_mappoints, n_obs, "mp_obs"))) return rc;   // before any copy
-    ORB_HIP_TRY(hipSetDevice(device));
-    g_mm.use_device(device);
+    if ((rc = check_csr(mp_obs_off, n_mappoints, n_obs, "mp_obs"))) return rc;   // before any copy
     const size_t M = n_mappoints, n = n_obs;
-    MmIo io;
+    Mirror io;
     io.add(mp_obs_off, M + 1, true, false); io.add(mp_obs_kf, n, true, false); io.add(mp_obs_idx, n, true, false);
     io.add(out_off, M + 1, false, true); io.add(out_kf, n, true, true); io.add(out_idx, n, true, true);
-    if ((rc = io.upload(g_mm.io))) return rc;
-    if ((rc = orbmm_compact_observations_device(n_mappoints, n_obs, mp_obs_off, mp_obs_kf, mp_obs_idx, out_off, out_kf, out_idx,
-                                                nullptr)))
-        return rc;
-    ORB_HIP_TRY(hipStreamSynchronize(nullptr));
-    return io.download();
+    return run_host(g_mm, device, io, [&] {
+        return orbmm_compact_observations_device(n_mappoints, n_obs, mp_obs_off, mp_obs_kf, mp_obs_idx, out_off, out_kf, out_idx,
+                                                 nullptr);
+    });
 }
-
-extern "C" int orbmm_children_live(int32_t n_keyframes, const int32_t* kf_parent, const uint8_t* kf_bad, int32_t* kf_child_off,
-                                   int32_t* kf_child_idx, int device) {
-    ORB_CHECK_ARG(n_keyframes >= 0, "negative sizes");
-    ORB_CHECK_ARG(kf_child_off && (n_keyframes == 0 || (kf_parent && kf_bad && kf_child_idx)), "null children array");
-    int rc;
-    if ((rc = mm_check_range(kf_parent, n_keyframes, -1, n_keyframes, "kf_parent outside [-1, n_keyframes)"))) return rc;
-    if (n_keyframes == 0) {
-        kf_child_off[0] = 0;
-        return ORB_OK;
-    }
-    ORB_HIP_TRY(hipSetDevice(device));
-    g_mm.use_device(device);
-    const size_t K = n_keyframes;
-    MmIo io;
-    io.add(kf_parent, K, true, false); io.add(kf_bad, K, true, false); io.add(kf_child_off, K + 1, false, true);
-    io.add(kf_child_idx, K, true, true);
-    if ((rc = io.upload(g_mm.io))) return rc;
-    if ((rc = orbmm_children_live_device(n_keyframes, kf_parent, kf_bad, kf_child_off, kf_child_idx, nullptr))) return rc;
-    ORB_HIP_TRY(hipStreamSynchronize(nullptr));
-    return io.download();
-}
-
-#include "orbmm_observe.inc"

@@ -1,5 +1,6 @@
-// Observation edits (include/orbslam2_amd.h, "Observation edits"; the rules are csrc/mm_observe.h's), the tail of
-// orbmm.hip: it shares that file's groups, staging and checks.
+// orbmm_observe.hip — observation edits on gfx950 (include/orbslam2_amd.h, "Observation edits"; the rules are
+// csrc/mm_observe.h's).  The lane groups and the scan are csrc/mm_groups.h's, the per-thread buffers and the table checks
+// orbmm.hip's entries share csrc/mm_host.h's.
 //   mm_obs_new_kernel     one thread per entry of the new keyframe's row: IsInKeyFrame, else AddObservation on the
 //                         point's row (the points of a row are distinct: a row has one writer)
 //   mm_obs_lists_kernel   one workgroup: the two stable compactions (added, recent) and their counts
@@ -7,6 +8,11 @@
 //                         LDS, the hits are taken one after another on uniformly loaded values, Replace's union is spread
 //                         over all lanes; a last scan turns the touched flags into the list
 //   mm_grow_*_kernel      the CSR with slack: count per point, one 64-bit scan by one workgroup, fill
+#include <algorithm>
+
+#include "common.h"
+#include "mm_groups.h"
+#include "mm_host.h"
 #include "mm_observe.h"
 
 namespace orbamd {
@@ -60,31 +66,8 @@ __global__ __launch_bounds__(256) void mm_grow_count_kernel(int M, int n_obs, co
 // Exclusive scan of out_off[0 .. M) in place by one workgroup of 256, summed in 64 bits; an offset past n_out is stored
 // as n_out + 1 (nothing is written from there on).  *status: the total does not fit.
 __global__ __launch_bounds__(256) void mm_grow_scan_kernel(int M, int n_out, int32_t* out_off, int32_t* status) {
-    __shared__ long long s_wave[4];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    long long carry = 0;
-    for (int base = 0; base < M; base += 256) {   // uniform trip count
-        const int i = base + (int)threadIdx.x;
-        const long long v = i < M ? ::max(out_off[i], 0) : 0;
-        long long x = v;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const long long y = __shfl_up(x, d, 64);
-            if (lane >= d) x += y;
-        }
-        if (lane == 63) s_wave[wave] = x;
-        __syncthreads();
-        long long before = 0;
-        for (int q = 0; q < wave; q++) before += s_wave[q];
-        const long long total = (s_wave[0] + s_wave[1]) + (s_wave[2] + s_wave[3]);
-        if (i < M) out_off[i] = (int32_t)::min(carry + before + x - v, (long long)n_out + 1);
-        carry += total;
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) {
-        out_off[M] = (int32_t)::min(carry, (long long)n_out + 1);
-        *status = carry > n_out ? MM_OBS_OVERFLOW : MM_OK;
-    }
+    const long long total = mm_block_scan<long long>(out_off, M, out_off, 0, 0x7fffffff, 0, (long long)n_out + 1);
+    if (threadIdx.x == 0) *status = total > n_out ? MM_OBS_OVERFLOW : MM_OK;
 }
 
 __global__ __launch_bounds__(256) void mm_grow_fill_kernel(int M, int n_obs, const int32_t* off, const int32_t* kf,
@@ -99,6 +82,8 @@ __global__ __launch_bounds__(256) void mm_grow_fill_kernel(int M, int n_obs, con
 }
 
 }  // namespace orbamd
+
+using namespace orbamd;
 
 namespace {
 
@@ -123,9 +108,9 @@ int mm_observe_check(const orbmm_observe* o, bool replace) {
 int mm_observe_check_host(const orbmm_observe* o, bool replace) {
     const int K = o->n_keyframes, M = o->n_mappoints;
     int rc;
-    if ((rc = mm_check_csr(o->mp_obs_off, M, o->n_obs, "mp_obs"))) return rc;
-    if ((rc = mm_check_range(o->kf_n, K, 0, o->kf_cap + 1, "kf_n outside [0, kf_cap]"))) return rc;
-    if ((rc = mm_check_range(o->kf_mappoint, (size_t)K * o->kf_cap, -1, M, "kf_mappoint entry outside [-1, n_mappoints)"))) return rc;
+    if ((rc = check_csr(o->mp_obs_off, M, o->n_obs, "mp_obs"))) return rc;
+    if ((rc = check_range(o->kf_n, K, 0, o->kf_cap + 1, "kf_n outside [0, kf_cap]"))) return rc;
+    if ((rc = check_range(o->kf_mappoint, (size_t)K * o->kf_cap, -1, M, "kf_mappoint entry outside [-1, n_mappoints)"))) return rc;
     for (int p = 0; p < M; p++) {
         int last = -1;
         for (int e = o->mp_obs_off[p]; e < o->mp_obs_off[p + 1]; e++) {
@@ -138,19 +123,12 @@ int mm_observe_check_host(const orbmm_observe* o, bool replace) {
             last = k;
         }
     }
-    std::vector<int32_t> seen(M, -1);
-    for (int k = 0; k < K; k++)
-        for (int i = 0; i < o->kf_n[k]; i++) {
-            const int p = o->kf_mappoint[(size_t)k * o->kf_cap + i];
-            if (p < 0) continue;
-            ORB_CHECK_ARG(seen[p] != k, "a map point twice in a keyframe's row");
-            seen[p] = k;
-        }
-    if (replace && (rc = mm_check_range(o->mp_replaced, M, -1, M, "mp_replaced outside [-1, n_mappoints)"))) return rc;
+    if ((rc = mm_check_rows_distinct(K, M, o->kf_cap, o->kf_n, o->kf_mappoint))) return rc;
+    if (replace && (rc = check_range(o->mp_replaced, M, -1, M, "mp_replaced outside [-1, n_mappoints)"))) return rc;
     return ORB_OK;
 }
 
-void mm_observe_add(MmIo& io, orbmm_observe& d, bool replace) {
+void mm_observe_add(Mirror& io, orbmm_observe& d, bool replace) {
     const size_t K = d.n_keyframes, M = d.n_mappoints, n_obs = d.n_obs;
     io.add(d.kf_n, K, true, false); io.add(d.kf_mappoint, K * d.kf_cap, true, true); io.add(d.kf_uright, K * d.kf_cap, true, false);
     io.add(d.mp_bad, M, true, replace); io.add(d.mp_nobs, M, true, true); io.add(d.mp_obs_off, M + 1, true, false);
@@ -174,12 +152,12 @@ int mm_apply_check(const orbmm_observe* o, const orbmm_apply* a) {
 
 int mm_apply_check_host(const orbmm_observe* o, const orbmm_apply* a) {
     int rc;
-    if ((rc = mm_check_csr(a->mp_begin, a->n_items, a->n_entries, "mp_begin"))) return rc;
-    if ((rc = mm_check_range(a->item_kf, a->n_items, 0, o->n_keyframes, "item_kf outside [0, n_keyframes)"))) return rc;
-    if ((rc = mm_check_range(a->point, a->n_entries, -1, o->n_mappoints, "point outside [-1, n_mappoints)"))) return rc;
-    if ((rc = mm_check_range(a->best_idx, a->n_entries, -1, o->kf_cap, "best_idx outside [-1, kf_cap)"))) return rc;
+    if ((rc = check_csr(a->mp_begin, a->n_items, a->n_entries, "mp_begin"))) return rc;
+    if ((rc = check_range(a->item_kf, a->n_items, 0, o->n_keyframes, "item_kf outside [0, n_keyframes)"))) return rc;
+    if ((rc = check_range(a->point, a->n_entries, -1, o->n_mappoints, "point outside [-1, n_mappoints)"))) return rc;
+    if ((rc = check_range(a->best_idx, a->n_entries, -1, o->kf_cap, "best_idx outside [-1, kf_cap)"))) return rc;
     if (a->mode == ORBMM_APPLY_FUSE_SIM3 &&
-        (rc = mm_check_range(a->replace_point, a->n_entries, -1, o->n_mappoints, "replace_point outside [-1, n_mappoints)")))
+        (rc = check_range(a->replace_point, a->n_entries, -1, o->n_mappoints, "replace_point outside [-1, n_mappoints)")))
         return rc;
     const int32_t* pr = a->progress;
     ORB_CHECK_ARG(pr[0] >= 0 && pr[0] <= a->n_items && pr[1] >= 0 && pr[1] <= (a->mode == ORBMM_APPLY_FUSE_SIM3 ? 1 : 0) && pr[2] >= 0 &&
@@ -187,7 +165,7 @@ int mm_apply_check_host(const orbmm_observe* o, const orbmm_apply* a) {
                   "progress outside the list");
     if (pr[0] || pr[1] || pr[2]) {
         ORB_CHECK_ARG(*a->n_touched >= 0 && *a->n_touched <= o->n_mappoints, "n_touched outside [0, n_mappoints]");
-        if ((rc = mm_check_range(a->touched, *a->n_touched, 0, o->n_mappoints, "touched entry outside [0, n_mappoints)"))) return rc;
+        if ((rc = check_range(a->touched, *a->n_touched, 0, o->n_mappoints, "touched entry outside [0, n_mappoints)"))) return rc;
     }
     return ORB_OK;
 }
@@ -264,18 +242,15 @@ extern "C" int orbmm_add_keyframe_observations(const orbmm_observe* o, int32_t c
     ORB_CHECK_ARG(added && recent_out && counts && status, "null output");
     if ((rc = mm_observe_check_host(o, false))) return rc;   // before any copy
     ORB_CHECK_ARG(cur >= 0 && cur < o->n_keyframes, "cur outside [0, n_keyframes)");
-    ORB_HIP_TRY(hipSetDevice(device));
-    g_mm.use_device(device);
     orbmm_observe d = *o;
     d.mp_found = d.mp_visible = d.mp_replaced = nullptr;
-    MmIo io;
+    Mirror io;
     mm_observe_add(io, d, false);
     const size_t cap = o->kf_cap;
     io.add(added, cap, false, true); io.add(recent_out, cap, false, true); io.add(counts, 2, false, true); io.add(status, cap, false, true);
-    if ((rc = io.upload(g_mm.io))) return rc;
-    if ((rc = orbmm_add_keyframe_observations_device(&d, cur, added, recent_out, counts, status, nullptr))) return rc;
-    ORB_HIP_TRY(hipStreamSynchronize(nullptr));
-    return io.download();
+    return run_host(g_mm, device, io, [&] {
+        return orbmm_add_keyframe_observations_device(&d, cur, added, recent_out, counts, status, nullptr);
+    });
 }
 
 extern "C" int orbmm_fuse_apply(const orbmm_observe* o, const orbmm_apply* a, int device) {
@@ -284,21 +259,16 @@ extern "C" int orbmm_fuse_apply(const orbmm_observe* o, const orbmm_apply* a, in
     if ((rc = mm_apply_check(o, a))) return rc;
     if ((rc = mm_observe_check_host(o, true))) return rc;   // before any copy
     if ((rc = mm_apply_check_host(o, a))) return rc;
-    ORB_HIP_TRY(hipSetDevice(device));
-    g_mm.use_device(device);
     orbmm_observe d = *o;
     orbmm_apply w = *a;
-    MmIo io;
+    Mirror io;
     mm_observe_add(io, d, true);
     const size_t I = a->n_items, E = a->n_entries;
     io.add(w.item_kf, I, true, false); io.add(w.mp_begin, I + 1, true, false); io.add(w.point, E, true, false);
     io.add(w.best_idx, E, true, false); io.add(w.replace_point, E, true, true); io.add(w.n_fused, I, true, true);
     io.add(w.touched, (size_t)o->n_mappoints, true, true); io.add(w.n_touched, 1, true, true); io.add(w.progress, 4, true, true);
     io.add(w.status, 1, false, true);
-    if ((rc = io.upload(g_mm.io))) return rc;
-    if ((rc = orbmm_fuse_apply_device(&d, &w, nullptr))) return rc;
-    ORB_HIP_TRY(hipStreamSynchronize(nullptr));
-    return io.download();
+    return run_host(g_mm, device, io, [&] { return orbmm_fuse_apply_device(&d, &w, nullptr); });
 }
 
 extern "C" int orbmm_grow_observations(int32_t n_mappoints, int32_t n_obs, const int32_t* mp_obs_off, const int32_t* mp_obs_kf,
@@ -307,20 +277,16 @@ extern "C" int orbmm_grow_observations(int32_t n_mappoints, int32_t n_obs, const
     int rc;
     if ((rc = mm_grow_check(n_mappoints, n_obs, mp_obs_off, mp_obs_kf, mp_obs_idx, slack, n_obs_out, out_off, out_kf, out_idx, status)))
         return rc;
-    if ((rc = mm_check_csr(mp_obs_off, n_mappoints, n_obs, "mp_obs"))) return rc;   // before any copy
-    if (extra && (rc = mm_check_range(extra, n_mappoints, 0, 0x7fffffff, "extra must not be negative"))) return rc;
-    ORB_HIP_TRY(hipSetDevice(device));
-    g_mm.use_device(device);
+    if ((rc = check_csr(mp_obs_off, n_mappoints, n_obs, "mp_obs"))) return rc;   // before any copy
+    if (extra && (rc = check_range(extra, n_mappoints, 0, 0x7fffffff, "extra must not be negative"))) return rc;
     const size_t M = n_mappoints;
-    MmIo io;
+    Mirror io;
     io.add(mp_obs_off, M + 1, true, false); io.add(mp_obs_kf, (size_t)n_obs, true, false); io.add(mp_obs_idx, (size_t)n_obs, true, false);
     io.add(extra, M, true, false);
     io.add(out_off, M + 1, false, true); io.add(out_kf, (size_t)n_obs_out, true, true); io.add(out_idx, (size_t)n_obs_out, true, true);
     io.add(status, 1, false, true);
-    if ((rc = io.upload(g_mm.io))) return rc;
-    if ((rc = orbmm_grow_observations_device(n_mappoints, n_obs, mp_obs_off, mp_obs_kf, mp_obs_idx, slack, extra, n_obs_out, out_off,
-                                             out_kf, out_idx, status, nullptr)))
-        return rc;
-    ORB_HIP_TRY(hipStreamSynchronize(nullptr));
-    return io.download();
+    return run_host(g_mm, device, io, [&] {
+        return orbmm_grow_observations_device(n_mappoints, n_obs, mp_obs_off, mp_obs_kf, mp_obs_idx, slack, extra, n_obs_out,
+                                              out_off, out_kf, out_idx, status, nullptr);
+    });
 }

@@ -4,7 +4,7 @@
 //   orbp_layout.h  the workspace regions (plain C++, shared with the CPU layout check)
 //   orbp_grid.h    constants, PjArgs, pj_grid_kernel, GetFeaturesInArea's window and scan order,
 //                  CheckOrientation's bin selection, the projection float sequences
-//   orbp_host.h    PjScratch (device switch, workspace, upload), the shared batch checks
+//   orbp_host.h    PjScratch (workspace), the shared batch checks
 //   orbp_track.h   SearchByProjection(Frame&, const std::vector<MapPoint*>&, th): pj_score / pj_walk
 //   orbp_motion.h  the motion-model search (pjm_*) and the relocalisation search (reloc_*)
 //   orbp_init.h    SearchForInitialization (pi_*)
@@ -60,21 +60,15 @@ extern "C" int orbm_search_by_projection(const orbm_proj_batch* b, int32_t* kp_m
     for (size_t j = 0; j < M; j++)
         ORB_CHECK_ARG(!b->mp_valid[j] || (b->mp_level[j] >= 0 && b->mp_level[j] < b->n_levels),
                       "trackScaleLevel out of range (scaleFactors[predictedScale], ORBmatcher.cc:328)");
-    ORB_HIP_TRY(hipSetDevice(device));
-    g_pj.use_device(device);
     orbm_proj_batch d = *b;
-    int32_t *d_match, *d_n;
-    if ((rc = g_pj.upload({{b->kp_begin, F + 1, d.kp_begin}, {b->kp_xy, 2 * K, d.kp_xy}, {b->kp_octave, K, d.kp_octave},
-                           {b->kp_uright, K, d.kp_uright}, {b->kp_desc, 32 * K, d.kp_desc},
-                           {b->kp_claimed, K, d.kp_claimed}, {b->bounds, 4 * F, d.bounds},
-                           {b->mp_begin, F + 1, d.mp_begin}, {b->mp_valid, M, d.mp_valid}, {b->mp_proj, 3 * M, d.mp_proj},
-                           {b->mp_view_cos, M, d.mp_view_cos}, {b->mp_level, M, d.mp_level},
-                           {b->mp_desc, 32 * M, d.mp_desc}, {b->mp_has_obs, M, d.mp_has_obs}},
-                          {{K, d_match}, {F, d_n}})))
-        return rc;
-    if ((rc = orbm_search_by_projection_device(&d, d_match, d_n, nullptr))) return rc;
-    if ((rc = pj_download(kp_match, d_match, K))) return rc;
-    return pj_download(n_matches, d_n, F);
+    Mirror io;
+    io.add(d.kp_begin, F + 1, true, false); io.add(d.kp_xy, 2 * K, true, false); io.add(d.kp_octave, K, true, false);
+    io.add(d.kp_uright, K, true, false); io.add(d.kp_desc, 32 * K, true, false); io.add(d.kp_claimed, K, true, false);
+    io.add(d.bounds, 4 * F, true, false); io.add(d.mp_begin, F + 1, true, false); io.add(d.mp_valid, M, true, false);
+    io.add(d.mp_proj, 3 * M, true, false); io.add(d.mp_view_cos, M, true, false); io.add(d.mp_level, M, true, false);
+    io.add(d.mp_desc, 32 * M, true, false); io.add(d.mp_has_obs, M, true, false);
+    io.add(kp_match, K, false, true); io.add(n_matches, F, false, true);
+    return run_host(g_pj, device, io, [&] { return orbm_search_by_projection_device(&d, kp_match, n_matches, nullptr); });
 }
 
 // ---------------------------------------------------------------- SearchByProjection(Frame&, const Frame&, th, mono)
@@ -136,20 +130,14 @@ extern "C" int orbm_search_for_initialization(const orbm_init_batch* b, int32_t*
         for (size_t q = 0; q < Q; q++)
             ORB_CHECK_ARG(b->q_angle[q] >= 0.f && b->q_angle[q] < 360.f, "keypoint angle outside [0, 360) (CV_Assert in CheckOrientation)");
     }
-    ORB_HIP_TRY(hipSetDevice(device));
-    g_pj.use_device(device);
     orbm_init_batch d = *b;   // d.prev_matched: the uploaded copy, which the device entry updates in place
-    int32_t *d_m12, *d_n;
-    if ((rc = g_pj.upload({{b->kp_begin, P + 1, d.kp_begin}, {b->kp_xy, 2 * K, d.kp_xy}, {b->kp_octave, K, d.kp_octave},
-                           {b->kp_desc, 32 * K, d.kp_desc}, {b->kp_angle, K, d.kp_angle}, {b->bounds, 4 * P, d.bounds},
-                           {b->q_begin, P + 1, d.q_begin}, {b->q_octave, Q, d.q_octave}, {b->q_desc, 32 * Q, d.q_desc},
-                           {b->q_angle, Q, d.q_angle}, {b->prev_matched, 2 * Q, d.prev_matched}},
-                          {{Q, d_m12}, {P, d_n}})))
-        return rc;
-    if ((rc = orbm_search_for_initialization_device(&d, d_m12, d_n, nullptr))) return rc;
-    if ((rc = pj_download(matches12, d_m12, Q))) return rc;
-    if ((rc = pj_download(b->prev_matched, d.prev_matched, 2 * Q))) return rc;
-    return pj_download(n_matches, d_n, P);
+    Mirror io;
+    io.add(d.kp_begin, P + 1, true, false); io.add(d.kp_xy, 2 * K, true, false); io.add(d.kp_octave, K, true, false);
+    io.add(d.kp_desc, 32 * K, true, false); io.add(d.kp_angle, K, true, false); io.add(d.bounds, 4 * P, true, false);
+    io.add(d.q_begin, P + 1, true, false); io.add(d.q_octave, Q, true, false); io.add(d.q_desc, 32 * Q, true, false);
+    io.add(d.q_angle, Q, true, false); io.add(d.prev_matched, 2 * Q, true, true);
+    io.add(matches12, Q, false, true); io.add(n_matches, P, false, true);
+    return run_host(g_pj, device, io, [&] { return orbm_search_for_initialization_device(&d, matches12, n_matches, nullptr); });
 }
 
 // ---------------------------------------------------------------- SearchByProjection(Frame&, KeyFrame*, alreadyFound, th, ORBdist)
@@ -189,21 +177,15 @@ extern "C" int orbm_search_by_projection_reloc(const orbm_reloc_batch* b, int32_
     if ((rc = pj_check_offsets(b->n_frames, b->kp_begin, b->total_kp, b->mp_begin, b->total_mp, false, PJ_ENDS_MSG,
                                PJ_FRAME_LIMIT_MSG)))
         return rc;
-    ORB_HIP_TRY(hipSetDevice(device));
-    g_pj.use_device(device);
     orbm_reloc_batch d = *b;
-    int32_t *d_match, *d_n;
-    if ((rc = g_pj.upload({{b->kp_begin, F + 1, d.kp_begin}, {b->kp_xy, 2 * K, d.kp_xy}, {b->kp_octave, K, d.kp_octave},
-                           {b->kp_desc, 32 * K, d.kp_desc}, {b->kp_angle, K, d.kp_angle}, {b->kp_claimed, K, d.kp_claimed},
-                           {b->bounds, 4 * F, d.bounds}, {b->pose, 12 * F, d.pose}, {b->camera, 4 * F, d.camera},
-                           {b->mp_begin, F + 1, d.mp_begin}, {b->mp_valid, M, d.mp_valid}, {b->mp_xw, 3 * M, d.mp_xw},
-                           {b->mp_max_min, 2 * M, d.mp_max_min}, {b->mp_desc, 32 * M, d.mp_desc},
-                           {b->mp_angle, M, d.mp_angle}},
-                          {{K, d_match}, {F, d_n}})))
-        return rc;
-    if ((rc = orbm_search_by_projection_reloc_device(&d, d_match, d_n, nullptr))) return rc;
-    if ((rc = pj_download(kp_match, d_match, K))) return rc;
-    return pj_download(n_matches, d_n, F);
+    Mirror io;
+    io.add(d.kp_begin, F + 1, true, false); io.add(d.kp_xy, 2 * K, true, false); io.add(d.kp_octave, K, true, false);
+    io.add(d.kp_desc, 32 * K, true, false); io.add(d.kp_angle, K, true, false); io.add(d.kp_claimed, K, true, false);
+    io.add(d.bounds, 4 * F, true, false); io.add(d.pose, 12 * F, true, false); io.add(d.camera, 4 * F, true, false);
+    io.add(d.mp_begin, F + 1, true, false); io.add(d.mp_valid, M, true, false); io.add(d.mp_xw, 3 * M, true, false);
+    io.add(d.mp_max_min, 2 * M, true, false); io.add(d.mp_desc, 32 * M, true, false); io.add(d.mp_angle, M, true, false);
+    io.add(kp_match, K, false, true); io.add(n_matches, F, false, true);
+    return run_host(g_pj, device, io, [&] { return orbm_search_by_projection_reloc_device(&d, kp_match, n_matches, nullptr); });
 }
 
 // ---------------------------------------------------------------- Fuse
@@ -235,15 +217,11 @@ extern "C" int orbm_fuse(const orbm_fuse_batch* b, int32_t* best_idx, int32_t* b
     if ((rc = pj_check_offsets(b->n_items, b->kp_begin, b->total_kp, b->mp_begin, b->total_mp, false, PJ_ENDS_MSG,
                                PJ_KEYFRAME_LIMIT_MSG)))
         return rc;
-    ORB_HIP_TRY(hipSetDevice(device));
-    g_pj.use_device(device);
-    orbm_fuse_batch d;
-    const uint8_t* d_claimed;
-    int32_t *d_idx, *d_dist, *d_n;
-    if ((rc = fuse_upload(g_pj, b, nullptr, d, d_claimed, {{M, d_idx}, {M, d_dist}, {F, d_n}}))) return rc;
-    if ((rc = orbm_fuse_device(&d, d_idx, d_dist, d_n, nullptr))) return rc;
-    if ((rc = pj_download(best_idx, d_idx, M)) || (rc = pj_download(best_dist, d_dist, M))) return rc;
-    return pj_download(n_fused, d_n, F);
+    orbm_fuse_batch d = *b;
+    Mirror io;
+    fuse_mirror(io, d);
+    io.add(best_idx, M, false, true); io.add(best_dist, M, false, true); io.add(n_fused, F, false, true);
+    return run_host(g_pj, device, io, [&] { return orbm_fuse_device(&d, best_idx, best_dist, n_fused, nullptr); });
 }
 
 // ---------------------------------------------------------------- SearchByProjection(const KeyFrame*, const Sim3&, ...)
@@ -279,15 +257,13 @@ extern "C" int orbm_search_by_projection_sim3(const orbm_fuse_batch* b, const ui
     if ((rc = pj_check_offsets(b->n_items, b->kp_begin, b->total_kp, b->mp_begin, b->total_mp, false, PJ_ENDS_MSG,
                                PJ_KEYFRAME_LIMIT_MSG)))
         return rc;
-    ORB_HIP_TRY(hipSetDevice(device));
-    g_pj.use_device(device);
-    orbm_fuse_batch d;
-    const uint8_t* d_claimed;
-    int32_t *d_match, *d_n;
-    if ((rc = fuse_upload(g_pj, b, kp_claimed, d, d_claimed, {{K, d_match}, {F, d_n}}))) return rc;
-    if ((rc = orbm_search_by_projection_sim3_device(&d, d_claimed, d_match, d_n, nullptr))) return rc;
-    if ((rc = pj_download(kp_match, d_match, K))) return rc;
-    return pj_download(n_matches, d_n, F);
+    orbm_fuse_batch d = *b;
+    Mirror io;
+    fuse_mirror(io, d);
+    io.add(kp_claimed, K, true, false); io.add(kp_match, K, false, true); io.add(n_matches, F, false, true);
+    return run_host(g_pj, device, io, [&] {
+        return orbm_search_by_projection_sim3_device(&d, kp_claimed, kp_match, n_matches, nullptr);
+    });
 }
 
 // ---------------------------------------------------------------- SearchBySim3
@@ -317,14 +293,10 @@ extern "C" int orbm_search_by_sim3(const orbm_sim3_batch* b, int32_t* match12, i
                                "kp1_begin / kp2_begin must start at 0 and end at total_kp1 / total_kp2",
                                PJ_KEYFRAME_LIMIT_MSG)))
         return rc;
-    ORB_HIP_TRY(hipSetDevice(device));
-    g_pj.use_device(device);
-    orbm_sim3_batch d;
-    int32_t *d_m12, *d_m1, *d_m2, *d_n;
-    if ((rc = sim3_upload(g_pj, b, d, {{K1, d_m12}, {K1, d_m1}, {K2, d_m2}, {F, d_n}}))) return rc;
-    if ((rc = orbm_search_by_sim3_device(&d, d_m12, d_m1, d_m2, d_n, nullptr))) return rc;
-    if ((rc = pj_download(match12, d_m12, K1)) || (rc = pj_download(match1, d_m1, K1)) ||
-        (rc = pj_download(match2, d_m2, K2)))
-        return rc;
-    return pj_download(n_found, d_n, F);
+    orbm_sim3_batch d = *b;
+    Mirror io;
+    sim3_mirror(io, d);
+    io.add(match12, K1, false, true); io.add(match1, K1, false, true); io.add(match2, K2, false, true);
+    io.add(n_found, F, false, true);
+    return run_host(g_pj, device, io, [&] { return orbm_search_by_sim3_device(&d, match12, match1, match2, n_found, nullptr); });
 }

@@ -223,19 +223,14 @@ static int fuse_workspace(PjScratch& s, const orbm_fuse_batch* b, PjArgs& a, Fus
     return ORB_OK;
 }
 
-// A host batch copied into the scratch: `d` = the batch with device pointers (scale_factors / inv_sigma2
-// stay host), d_claimed = kp_claimed's copy or NULL, `out` = the entry's output arrays behind it.
-static int fuse_upload(PjScratch& s, const orbm_fuse_batch* b, const uint8_t* kp_claimed, orbm_fuse_batch& d,
-                       const uint8_t*& d_claimed, std::initializer_list<PjOut> out) {
-    const size_t F = b->n_items, K = b->total_kp, M = b->total_mp;
-    d = *b;
-    return s.upload({{b->kp_begin, F + 1, d.kp_begin}, {b->kp_xy, 2 * K, d.kp_xy}, {b->kp_octave, K, d.kp_octave},
-                     {b->kp_uright, K, d.kp_uright}, {b->kp_desc, 32 * K, d.kp_desc}, {kp_claimed, K, d_claimed},
-                     {b->bounds, 4 * F, d.bounds}, {b->pose, 12 * F, d.pose}, {b->camera, 5 * F, d.camera},
-                     {b->mp_begin, F + 1, d.mp_begin}, {b->mp_valid, M, d.mp_valid}, {b->mp_xw, 3 * M, d.mp_xw},
-                     {b->mp_max_min, 2 * M, d.mp_max_min}, {b->mp_normal, 3 * M, d.mp_normal},
-                     {b->mp_desc, 32 * M, d.mp_desc}},
-                    out);
+// The arrays of a host batch (scale_factors / inv_sigma2 stay host)
+static void fuse_mirror(Mirror& io, orbm_fuse_batch& d) {
+    const size_t F = d.n_items, K = d.total_kp, M = d.total_mp;
+    io.add(d.kp_begin, F + 1, true, false); io.add(d.kp_xy, 2 * K, true, false); io.add(d.kp_octave, K, true, false);
+    io.add(d.kp_uright, K, true, false); io.add(d.kp_desc, 32 * K, true, false); io.add(d.bounds, 4 * F, true, false);
+    io.add(d.pose, 12 * F, true, false); io.add(d.camera, 5 * F, true, false); io.add(d.mp_begin, F + 1, true, false);
+    io.add(d.mp_valid, M, true, false); io.add(d.mp_xw, 3 * M, true, false); io.add(d.mp_max_min, 2 * M, true, false);
+    io.add(d.mp_normal, 3 * M, true, false); io.add(d.mp_desc, 32 * M, true, false);
 }
 
 }  // namespace orbamd

@@ -1,53 +1,10 @@
 // The host side every projection entry shares (included by orbp.hip after orbp_grid.h): the per-thread
-// scratch with its workspace and upload helpers, and the batch checks.
+// scratch with its workspace helper, and the batch checks (the host entries stage with common.h's Mirror).
 #pragma once
 
 namespace orbamd {
 
-using orbamd_host::Carver;
-
-template <class T>
-static void pj_set_ptr(void* dst, char* p) { *static_cast<T**>(dst) = reinterpret_cast<T*>(p); }
-
-// One array of a host batch: n elements at src, copied to the device; *dst becomes the copy's address
-// (null when src is null: an optional array stays absent).
-struct PjIn {
-    const void* src;
-    size_t bytes;
-    void* dst;                    // the address of the pointer to set, and the setter that knows its type
-    void (*set)(void*, char*);
-    template <class T>
-    PjIn(const T* s, size_t n, const T*& d) : src(s), bytes(n * sizeof(T)), dst(&d), set(&pj_set_ptr<const T>) {}
-    template <class T>
-    PjIn(const T* s, size_t n, T*& d) : src(s), bytes(n * sizeof(T)), dst(&d), set(&pj_set_ptr<T>) {}
-};
-// One output array of n elements on the device, behind the inputs.
-struct PjOut {
-    size_t bytes;
-    void* dst;
-    void (*set)(void*, char*);
-    template <class T>
-    PjOut(size_t n, T*& d) : bytes(n * sizeof(T)), dst(&d), set(&pj_set_ptr<T>) {}
-};
-
-struct PjScratch {
-    DevBuf ws, io;
-    int device = -1;
-
-    void use_device(int dev) {
-        if (device != dev) {
-            ws.release();
-            io.release();
-            device = dev;
-        }
-    }
-    int use_current_device() {
-        int dev = 0;
-        ORB_HIP_TRY(hipGetDevice(&dev));
-        use_device(dev);
-        return ORB_OK;
-    }
-
+struct PjScratch : Scratch {
     // The workspace of a call: carve(Carver&) takes every field; a dry run sizes the buffer, the second
     // run hands out the pointers.
     template <class Fn>
@@ -60,38 +17,7 @@ struct PjScratch {
         carve(c);
         return ORB_OK;
     }
-
-    // A host batch into `io` with one reserve: the non-null inputs copied in order, then room for the
-    // outputs.  The callers pass the fields of a copy of the batch struct as dst, so that copy becomes the
-    // device entry's argument.
-    int upload(std::initializer_list<PjIn> in, std::initializer_list<PjOut> out) {
-        Carver dry{nullptr};
-        char* p;
-        for (const PjIn& i : in) dry.take(p, i.bytes);
-        for (const PjOut& o : out) dry.take(p, o.bytes);
-        int rc;
-        if ((rc = io.reserve(dry.off))) return rc;
-        Carver c{io.as<char>()};
-        for (const PjIn& i : in) {
-            c.take(p, i.bytes);
-            if (!i.src) p = nullptr;
-            if (p && i.bytes) ORB_HIP_TRY(hipMemcpy(p, i.src, i.bytes, hipMemcpyHostToDevice));
-            i.set(i.dst, p);
-        }
-        for (const PjOut& o : out) {
-            c.take(p, o.bytes);
-            o.set(o.dst, p);
-        }
-        return ORB_OK;
-    }
 };
-
-// n elements of an output back to the host (a null host array is one the caller did not ask for)
-template <class T>
-static int pj_download(T* host, const T* dev, size_t n) {
-    if (host && n) ORB_HIP_TRY(hipMemcpy(host, dev, n * sizeof(T), hipMemcpyDeviceToHost));
-    return ORB_OK;
-}
 
 static void pj_bind(PjArgs& a, const orbamd_host::PjGridLayout& g) {
     a.grid_idx = g.grid_idx;

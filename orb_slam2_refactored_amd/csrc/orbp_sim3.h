@@ -262,22 +262,19 @@ static int sim3_common(const orbm_sim3_batch* b, Sim3Args& a) {
     return ORB_OK;
 }
 
-// A host batch copied into the scratch: `d` = the batch with device pointers (scale_factors stays host),
-// `out` = the entry's output arrays behind it.
-static int sim3_upload(PjScratch& s, const orbm_sim3_batch* b, orbm_sim3_batch& d, std::initializer_list<PjOut> out) {
-    const size_t F = b->n_pairs, K1 = b->total_kp1, K2 = b->total_kp2;
-    d = *b;
-    return s.upload({{b->kp1_begin, F + 1, d.kp1_begin}, {b->kp2_begin, F + 1, d.kp2_begin},
-                     {b->kp1_xy, 2 * K1, d.kp1_xy}, {b->kp1_octave, K1, d.kp1_octave}, {b->kp1_desc, 32 * K1, d.kp1_desc},
-                     {b->kp2_xy, 2 * K2, d.kp2_xy}, {b->kp2_octave, K2, d.kp2_octave}, {b->kp2_desc, 32 * K2, d.kp2_desc},
-                     {b->bounds1, 4 * F, d.bounds1}, {b->pose1, 12 * F, d.pose1}, {b->camera1, 4 * F, d.camera1},
-                     {b->bounds2, 4 * F, d.bounds2}, {b->pose2, 12 * F, d.pose2}, {b->camera2, 4 * F, d.camera2},
-                     {b->mp1_valid, K1, d.mp1_valid}, {b->mp1_xw, 3 * K1, d.mp1_xw}, {b->mp1_max_min, 2 * K1, d.mp1_max_min},
-                     {b->mp1_desc, 32 * K1, d.mp1_desc},
-                     {b->mp2_valid, K2, d.mp2_valid}, {b->mp2_xw, 3 * K2, d.mp2_xw}, {b->mp2_max_min, 2 * K2, d.mp2_max_min},
-                     {b->mp2_desc, 32 * K2, d.mp2_desc},
-                     {b->s12, 13 * F, d.s12}},
-                    out);
+// The arrays of a host batch (scale_factors stays host)
+static void sim3_mirror(Mirror& io, orbm_sim3_batch& d) {
+    const size_t F = d.n_pairs, K1 = d.total_kp1, K2 = d.total_kp2;
+    io.add(d.kp1_begin, F + 1, true, false); io.add(d.kp2_begin, F + 1, true, false);
+    io.add(d.kp1_xy, 2 * K1, true, false); io.add(d.kp1_octave, K1, true, false); io.add(d.kp1_desc, 32 * K1, true, false);
+    io.add(d.kp2_xy, 2 * K2, true, false); io.add(d.kp2_octave, K2, true, false); io.add(d.kp2_desc, 32 * K2, true, false);
+    io.add(d.bounds1, 4 * F, true, false); io.add(d.pose1, 12 * F, true, false); io.add(d.camera1, 4 * F, true, false);
+    io.add(d.bounds2, 4 * F, true, false); io.add(d.pose2, 12 * F, true, false); io.add(d.camera2, 4 * F, true, false);
+    io.add(d.mp1_valid, K1, true, false); io.add(d.mp1_xw, 3 * K1, true, false); io.add(d.mp1_max_min, 2 * K1, true, false);
+    io.add(d.mp1_desc, 32 * K1, true, false);
+    io.add(d.mp2_valid, K2, true, false); io.add(d.mp2_xw, 3 * K2, true, false); io.add(d.mp2_max_min, 2 * K2, true, false);
+    io.add(d.mp2_desc, 32 * K2, true, false);
+    io.add(d.s12, 13 * F, true, false);
 }
 
 }  // namespace orbamd

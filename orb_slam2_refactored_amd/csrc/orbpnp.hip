@@ -399,18 +399,11 @@ struct PnPCapEntry {
     DevBuf buf;
 };
 
-struct PnPScratch {
-    DevBuf ws, io;
+struct PnPScratch : Scratch {
     PnPCapEntry caps[4];   // the tables of the last parameter sets, uploaded once each
     int next_cap = 0;
-    int device = -1;
-    void use_device(int dev) {
-        if (device != dev) {
-            ws.release();
-            io.release();
-            for (PnPCapEntry& c : caps) { c.buf.release(); c.max_iterations = 0; }
-            device = dev;
-        }
+    void device_changed() override {
+        for (PnPCapEntry& c : caps) { c.buf.release(); c.max_iterations = 0; }
     }
     int cap_table(double probability, int min_inliers, int max_iterations, float epsilon, const int32_t** out) {
         for (PnPCapEntry& c : caps)
@@ -481,9 +474,7 @@ extern "C" int orb_pnpsolver_iterate_device(const orb_pnpsolver_batch* in, orb_p
     int rc;
     if ((rc = pnp_common(in, out, a))) return rc;
     if (in->n_frames == 0) return ORB_OK;
-    int dev = 0;
-    ORB_HIP_TRY(hipGetDevice(&dev));
-    g_pnp.use_device(dev);
+    if ((rc = g_pnp.use_current_device())) return rc;
     if ((rc = g_pnp.cap_table(in->probability, in->min_inliers, in->max_iterations, in->epsilon, &a.caps))) return rc;
     const size_t K = std::max<size_t>(in->total_kp, 1), F = in->n_frames;
     const size_t o_recs = 0, o_slots = o_recs + align_up(K * sizeof(PnPRec), 256), o_info = o_slots + align_up(K * 4, 256),
@@ -531,44 +522,16 @@ extern "C" int orb_pnpsolver_iterate(const orb_pnpsolver_batch* in, orb_pnpsolve
     const size_t n_draws = F * in->n_draws * 4;
     for (size_t j = 0; j < n_draws; j++)
         ORB_CHECK_ARG(in->draws[j] >= 0 && in->draws[j] <= in->rand_max, "draws must lie in [0, rand_max]");
-    ORB_HIP_TRY(hipSetDevice(device));
-    g_pnp.use_device(device);
-    size_t off = 0;
-    auto take = [&](size_t bytes) { const size_t o = off; off += align_up(std::max<size_t>(bytes, 1), 256); return o; };
-    struct In { const void* src; size_t bytes; size_t at; };
-    In ins[] = {{kb, (F + 1) * 4, 0}, {in->kp_xy, K * 8, 0}, {in->kp_octave, K * 4, 0}, {in->camera, F * 16, 0},
-                {in->mp_valid, K, 0}, {in->mp_xw, K * 12, 0}, {in->draws, n_draws * 4, 0},
-                {out->iterations, F * 4, 0}, {out->best_inliers, F * 4, 0}, {out->best_mask, K, 0}, {out->best_tcw, F * 48, 0}};
-    for (In& i : ins) i.at = take(i.bytes);
-    const size_t H = out->hyp_inliers ? F * in->n_draws * 4 : 0;
-    const size_t o_tcw = take(F * 48), o_inl = take(K), o_found = take(F * 4), o_n = take(F * 4), o_term = take(F * 4), o_hyp = take(H);
-    if ((rc = g_pnp.io.reserve(off))) return rc;
-    char* b = g_pnp.io.as<char>();
-    for (const In& i : ins)
-        if (i.bytes) ORB_HIP_TRY(hipMemcpy(b + i.at, i.src, i.bytes, hipMemcpyHostToDevice));
     orb_pnpsolver_batch d = *in;
-    d.kp_begin = (const int32_t*)(b + ins[0].at); d.kp_xy = (const float*)(b + ins[1].at);
-    d.kp_octave = (const int32_t*)(b + ins[2].at); d.camera = (const float*)(b + ins[3].at);
-    d.mp_valid = (const uint8_t*)(b + ins[4].at); d.mp_xw = (const float*)(b + ins[5].at);
-    d.draws = (const int32_t*)(b + ins[6].at);
-    orb_pnpsolver_result r{};
-    r.tcw = (float*)(b + o_tcw); r.inlier = (uint8_t*)(b + o_inl); r.found = (int32_t*)(b + o_found);
-    r.n_inliers = (int32_t*)(b + o_n); r.terminate = (int32_t*)(b + o_term);
-    r.iterations = (int32_t*)(b + ins[7].at); r.best_inliers = (int32_t*)(b + ins[8].at);
-    r.best_mask = (uint8_t*)(b + ins[9].at); r.best_tcw = (float*)(b + ins[10].at);
-    r.hyp_inliers = H ? (int32_t*)(b + o_hyp) : nullptr;
-    if ((rc = orb_pnpsolver_iterate_device(&d, &r, nullptr))) return rc;
-    ORB_HIP_TRY(hipMemcpy(out->tcw, r.tcw, F * 48, hipMemcpyDeviceToHost));   // (synchronises with the null stream)
-    if (K) {
-        ORB_HIP_TRY(hipMemcpy(out->inlier, r.inlier, K, hipMemcpyDeviceToHost));
-        ORB_HIP_TRY(hipMemcpy(out->best_mask, r.best_mask, K, hipMemcpyDeviceToHost));
-    }
-    ORB_HIP_TRY(hipMemcpy(out->found, r.found, F * 4, hipMemcpyDeviceToHost));
-    ORB_HIP_TRY(hipMemcpy(out->n_inliers, r.n_inliers, F * 4, hipMemcpyDeviceToHost));
-    ORB_HIP_TRY(hipMemcpy(out->terminate, r.terminate, F * 4, hipMemcpyDeviceToHost));
-    ORB_HIP_TRY(hipMemcpy(out->iterations, r.iterations, F * 4, hipMemcpyDeviceToHost));
-    ORB_HIP_TRY(hipMemcpy(out->best_inliers, r.best_inliers, F * 4, hipMemcpyDeviceToHost));
-    ORB_HIP_TRY(hipMemcpy(out->best_tcw, r.best_tcw, F * 48, hipMemcpyDeviceToHost));
-    if (H) ORB_HIP_TRY(hipMemcpy(out->hyp_inliers, r.hyp_inliers, H, hipMemcpyDeviceToHost));
-    return ORB_OK;
+    orb_pnpsolver_result r = *out;
+    Mirror io;
+    io.add(d.kp_begin, F + 1, true, false); io.add(d.kp_xy, K * 2, true, false); io.add(d.kp_octave, K, true, false);
+    io.add(d.camera, F * 4, true, false); io.add(d.mp_valid, K, true, false); io.add(d.mp_xw, K * 3, true, false);
+    io.add(d.draws, n_draws, true, false);
+    io.add(r.iterations, F, true, true); io.add(r.best_inliers, F, true, true); io.add(r.best_mask, K, true, true);
+    io.add(r.best_tcw, F * 12, true, true);
+    io.add(r.tcw, F * 12, false, true); io.add(r.inlier, K, false, true); io.add(r.found, F, false, true);
+    io.add(r.n_inliers, F, false, true); io.add(r.terminate, F, false, true);
+    io.add(r.hyp_inliers, F * in->n_draws, false, true);
+    return run_host(g_pnp, device, io, [&] { return orb_pnpsolver_iterate_device(&d, &r, nullptr); });
 }

@@ -491,18 +491,7 @@ __global__ __launch_bounds__(S3_THREADS) void optimize_sim3_kernel(S3Args a) {
     }
 }
 
-struct S3Scratch {
-    DevBuf ws, io;
-    int device = -1;
-    void use_device(int dev) {
-        if (device != dev) {
-            ws.release();
-            io.release();
-            device = dev;
-        }
-    }
-};
-thread_local S3Scratch g_s3;
+thread_local Scratch g_s3;
 
 }  // namespace orbamd
 
@@ -545,9 +534,7 @@ extern "C" int orbba_optimize_sim3_device(const orbba_sim3_batch* in, orbba_sim3
     int rc;
     if ((rc = s3_common(in, out, a))) return rc;
     if (in->n_pairs == 0) return ORB_OK;
-    int dev = 0;
-    ORB_HIP_TRY(hipGetDevice(&dev));
-    g_s3.use_device(dev);
+    if ((rc = g_s3.use_current_device())) return rc;
     if ((rc = g_s3.ws.reserve(std::max<size_t>(in->total_kp1, 1) * sizeof(int32_t)))) return rc;
     a.slots = g_s3.ws.as<int32_t>();
     hipLaunchKernelGGL(optimize_sim3_kernel, dim3((a.n_pairs + S3_WAVES - 1) / S3_WAVES), dim3(S3_THREADS), 0,
@@ -579,37 +566,18 @@ extern "C" int orbba_optimize_sim3(const orbba_sim3_batch* in, orbba_sim3_result
     }
     for (size_t j = 0; j < K2; j++)
         ORB_CHECK_ARG(in->kp2_octave[j] >= 0 && in->kp2_octave[j] < in->n_levels, "kp2_octave out of range");
-    ORB_HIP_TRY(hipSetDevice(device));
-    g_s3.use_device(device);
-    size_t off = 0;
-    auto take = [&](size_t bytes) { const size_t o = off; off += align_up(std::max<size_t>(bytes, 1), 256); return o; };
-    struct In { const void* src; size_t bytes; size_t at; };
-    In ins[] = {{b1, (F + 1) * 4, 0}, {b2, (F + 1) * 4, 0}, {in->kp1_xy, K1 * 8, 0}, {in->kp2_xy, K2 * 8, 0},
-                {in->kp1_octave, K1 * 4, 0}, {in->kp2_octave, K2 * 4, 0}, {in->pose1, F * 48, 0}, {in->pose2, F * 48, 0},
-                {in->camera1, F * 16, 0}, {in->camera2, F * 16, 0}, {in->mp1_valid, K1, 0}, {in->mp2_valid, K2, 0},
-                {in->mp1_xw, K1 * 12, 0}, {in->mp2_xw, K2 * 12, 0}, {in->s12, F * 52, 0}, {in->match12, K1 * 4, 0}};
-    for (In& i : ins) i.at = take(i.bytes);
-    const size_t o_s12 = take(F * 52), o_g2o = take(F * 64), o_m = take(K1 * 4), o_n = take(F * 4), o_it = take(F * 8);
-    if ((rc = g_s3.io.reserve(off))) return rc;
-    char* b = g_s3.io.as<char>();
-    for (const In& i : ins)
-        if (i.bytes) ORB_HIP_TRY(hipMemcpy(b + i.at, i.src, i.bytes, hipMemcpyHostToDevice));
     orbba_sim3_batch d = *in;
-    d.kp1_begin = (const int32_t*)(b + ins[0].at); d.kp2_begin = (const int32_t*)(b + ins[1].at);
-    d.kp1_xy = (const float*)(b + ins[2].at); d.kp2_xy = (const float*)(b + ins[3].at);
-    d.kp1_octave = (const int32_t*)(b + ins[4].at); d.kp2_octave = (const int32_t*)(b + ins[5].at);
-    d.pose1 = (const float*)(b + ins[6].at); d.pose2 = (const float*)(b + ins[7].at);
-    d.camera1 = (const float*)(b + ins[8].at); d.camera2 = (const float*)(b + ins[9].at);
-    d.mp1_valid = (const uint8_t*)(b + ins[10].at); d.mp2_valid = (const uint8_t*)(b + ins[11].at);
-    d.mp1_xw = (const float*)(b + ins[12].at); d.mp2_xw = (const float*)(b + ins[13].at);
-    d.s12 = (const float*)(b + ins[14].at); d.match12 = (const int32_t*)(b + ins[15].at);
-    orbba_sim3_result r{(float*)(b + o_s12), (double*)(b + o_g2o), (int32_t*)(b + o_m), (int32_t*)(b + o_n),
-                        (int32_t*)(b + o_it)};
-    if ((rc = orbba_optimize_sim3_device(&d, &r, nullptr))) return rc;
-    ORB_HIP_TRY(hipMemcpy(out->s12, r.s12, F * 52, hipMemcpyDeviceToHost));   // (synchronises with the null stream)
-    if (out->s12_g2o) ORB_HIP_TRY(hipMemcpy(out->s12_g2o, r.s12_g2o, F * 64, hipMemcpyDeviceToHost));
-    if (K1) ORB_HIP_TRY(hipMemcpy(out->match12, r.match12, K1 * 4, hipMemcpyDeviceToHost));
-    ORB_HIP_TRY(hipMemcpy(out->n_inliers, r.n_inliers, F * 4, hipMemcpyDeviceToHost));
-    if (out->iterations) ORB_HIP_TRY(hipMemcpy(out->iterations, r.iterations, F * 8, hipMemcpyDeviceToHost));
-    return ORB_OK;
+    orbba_sim3_result r = *out;
+    Mirror io;
+    io.add(d.kp1_begin, F + 1, true, false); io.add(d.kp2_begin, F + 1, true, false);
+    io.add(d.kp1_xy, K1 * 2, true, false); io.add(d.kp2_xy, K2 * 2, true, false);
+    io.add(d.kp1_octave, K1, true, false); io.add(d.kp2_octave, K2, true, false);
+    io.add(d.pose1, F * 12, true, false); io.add(d.pose2, F * 12, true, false);
+    io.add(d.camera1, F * 4, true, false); io.add(d.camera2, F * 4, true, false);
+    io.add(d.mp1_valid, K1, true, false); io.add(d.mp2_valid, K2, true, false);
+    io.add(d.mp1_xw, K1 * 3, true, false); io.add(d.mp2_xw, K2 * 3, true, false);
+    io.add(d.s12, F * 13, true, false); io.add(d.match12, K1, true, false);
+    io.add(r.s12, F * 13, false, true); io.add(r.s12_g2o, F * 8, false, true); io.add(r.match12, K1, false, true);
+    io.add(r.n_inliers, F, false, true); io.add(r.iterations, F * 2, false, true);
+    return run_host(g_s3, device, io, [&] { return orbba_optimize_sim3_device(&d, &r, nullptr); });
 }

@@ -294,18 +294,11 @@ struct S3SCapEntry {
     DevBuf buf;
 };
 
-struct S3SScratch {
-    DevBuf ws, io;
+struct S3SScratch : Scratch {
     S3SCapEntry caps[4];   // the tables of the last parameter sets, uploaded once each
     int next_cap = 0;
-    int device = -1;
-    void use_device(int dev) {
-        if (device != dev) {
-            ws.release();
-            io.release();
-            for (S3SCapEntry& c : caps) { c.buf.release(); c.max_iterations = 0; }
-            device = dev;
-        }
+    void device_changed() override {
+        for (S3SCapEntry& c : caps) { c.buf.release(); c.max_iterations = 0; }
     }
     // The device copy of the cap table.  A new parameter set is uploaded with a synchronous copy (once, like
     // the workspace allocation); every later call with it enqueues nothing but the kernels.
@@ -383,9 +376,7 @@ extern "C" int orb_sim3solver_iterate_device(const orb_sim3solver_batch* in, orb
     int rc;
     if ((rc = s3s_common(in, out, a))) return rc;
     if (in->n_pairs == 0) return ORB_OK;
-    int dev = 0;
-    ORB_HIP_TRY(hipGetDevice(&dev));
-    g_s3s.use_device(dev);
+    if ((rc = g_s3s.use_current_device())) return rc;
     if ((rc = g_s3s.cap_table(in->probability, in->min_inliers, in->max_iterations, &a.caps))) return rc;
     const size_t K1 = std::max<size_t>(in->total_kp1, 1), F = in->n_pairs;
     const size_t o_recs = 0, o_slots = o_recs + align_up(K1 * sizeof(S3SRec), 256), o_info = o_slots + align_up(K1 * 4, 256),
@@ -431,49 +422,20 @@ extern "C" int orb_sim3solver_iterate(const orb_sim3solver_batch* in, orb_sim3so
     const size_t n_draws = F * in->max_iterations * 3;
     for (size_t j = 0; j < n_draws; j++)
         ORB_CHECK_ARG(in->draws[j] >= 0 && in->draws[j] <= in->rand_max, "draws must lie in [0, rand_max]");
-    ORB_HIP_TRY(hipSetDevice(device));
-    g_s3s.use_device(device);
-    size_t off = 0;
-    auto take = [&](size_t bytes) { const size_t o = off; off += align_up(std::max<size_t>(bytes, 1), 256); return o; };
-    struct In { const void* src; size_t bytes; size_t at; };
-    In ins[] = {{b1, (F + 1) * 4, 0}, {b2, (F + 1) * 4, 0}, {in->kp1_octave, K1 * 4, 0}, {in->kp2_octave, K2 * 4, 0},
-                {in->pose1, F * 48, 0}, {in->pose2, F * 48, 0}, {in->camera1, F * 16, 0}, {in->camera2, F * 16, 0},
-                {in->mp1_valid, K1, 0}, {in->mp2_valid, K2, 0}, {in->mp1_xw, K1 * 12, 0}, {in->mp2_xw, K2 * 12, 0},
-                {in->match12, K1 * 4, 0}, {in->draws, n_draws * 4, 0}, {out->iterations, F * 4, 0}, {out->max_inliers, F * 4, 0}};
-    for (In& i : ins) i.at = take(i.bytes);
-    const size_t H = out->hyp_inliers ? F * in->max_iterations * 4 : 0;
-    const size_t o_s12 = take(F * 52), o_inl = take(K1), o_m = take(K1 * 4), o_found = take(F * 4), o_n = take(F * 4),
-                 o_term = take(F * 4), o_hyp = take(H);
-    if ((rc = g_s3s.io.reserve(off))) return rc;
-    char* b = g_s3s.io.as<char>();
-    for (const In& i : ins)
-        if (i.bytes) ORB_HIP_TRY(hipMemcpy(b + i.at, i.src, i.bytes, hipMemcpyHostToDevice));
     orb_sim3solver_batch d = *in;
-    d.kp1_begin = (const int32_t*)(b + ins[0].at); d.kp2_begin = (const int32_t*)(b + ins[1].at);
     d.kp1_xy = nullptr; d.kp2_xy = nullptr; d.s12 = nullptr;
-    d.kp1_octave = (const int32_t*)(b + ins[2].at); d.kp2_octave = (const int32_t*)(b + ins[3].at);
-    d.pose1 = (const float*)(b + ins[4].at); d.pose2 = (const float*)(b + ins[5].at);
-    d.camera1 = (const float*)(b + ins[6].at); d.camera2 = (const float*)(b + ins[7].at);
-    d.mp1_valid = (const uint8_t*)(b + ins[8].at); d.mp2_valid = (const uint8_t*)(b + ins[9].at);
-    d.mp1_xw = (const float*)(b + ins[10].at); d.mp2_xw = (const float*)(b + ins[11].at);
-    d.match12 = (const int32_t*)(b + ins[12].at); d.draws = (const int32_t*)(b + ins[13].at);
-    orb_sim3solver_result r{};
-    r.s12 = (float*)(b + o_s12); r.inlier = (uint8_t*)(b + o_inl); r.match12 = (int32_t*)(b + o_m);
-    r.found = (int32_t*)(b + o_found); r.n_inliers = (int32_t*)(b + o_n);
-    r.iterations = (int32_t*)(b + ins[14].at); r.max_inliers = (int32_t*)(b + ins[15].at);
-    r.terminate = (int32_t*)(b + o_term);
-    r.hyp_inliers = H ? (int32_t*)(b + o_hyp) : nullptr;
-    if ((rc = orb_sim3solver_iterate_device(&d, &r, nullptr))) return rc;
-    ORB_HIP_TRY(hipMemcpy(out->s12, r.s12, F * 52, hipMemcpyDeviceToHost));   // (synchronises with the null stream)
-    if (K1) {
-        ORB_HIP_TRY(hipMemcpy(out->inlier, r.inlier, K1, hipMemcpyDeviceToHost));
-        ORB_HIP_TRY(hipMemcpy(out->match12, r.match12, K1 * 4, hipMemcpyDeviceToHost));
-    }
-    ORB_HIP_TRY(hipMemcpy(out->found, r.found, F * 4, hipMemcpyDeviceToHost));
-    ORB_HIP_TRY(hipMemcpy(out->n_inliers, r.n_inliers, F * 4, hipMemcpyDeviceToHost));
-    ORB_HIP_TRY(hipMemcpy(out->iterations, r.iterations, F * 4, hipMemcpyDeviceToHost));
-    ORB_HIP_TRY(hipMemcpy(out->max_inliers, r.max_inliers, F * 4, hipMemcpyDeviceToHost));
-    ORB_HIP_TRY(hipMemcpy(out->terminate, r.terminate, F * 4, hipMemcpyDeviceToHost));
-    if (H) ORB_HIP_TRY(hipMemcpy(out->hyp_inliers, r.hyp_inliers, H, hipMemcpyDeviceToHost));
-    return ORB_OK;
+    orb_sim3solver_result r = *out;
+    Mirror io;
+    io.add(d.kp1_begin, F + 1, true, false); io.add(d.kp2_begin, F + 1, true, false);
+    io.add(d.kp1_octave, K1, true, false); io.add(d.kp2_octave, K2, true, false);
+    io.add(d.pose1, F * 12, true, false); io.add(d.pose2, F * 12, true, false);
+    io.add(d.camera1, F * 4, true, false); io.add(d.camera2, F * 4, true, false);
+    io.add(d.mp1_valid, K1, true, false); io.add(d.mp2_valid, K2, true, false);
+    io.add(d.mp1_xw, K1 * 3, true, false); io.add(d.mp2_xw, K2 * 3, true, false);
+    io.add(d.match12, K1, true, false); io.add(d.draws, n_draws, true, false);
+    io.add(r.iterations, F, true, true); io.add(r.max_inliers, F, true, true);
+    io.add(r.s12, F * 13, false, true); io.add(r.inlier, K1, false, true); io.add(r.match12, K1, false, true);
+    io.add(r.found, F, false, true); io.add(r.n_inliers, F, false, true); io.add(r.terminate, F, false, true);
+    io.add(r.hyp_inliers, F * in->max_iterations, false, true);
+    return run_host(g_s3s, device, io, [&] { return orb_sim3solver_iterate_device(&d, &r, nullptr); });
 }

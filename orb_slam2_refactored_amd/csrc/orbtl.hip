@@ -316,25 +316,13 @@ __global__ __launch_bounds__(256) void tl_gather_kernel(orbtl_map m, orbtl_frame
     reinterpret_cast<uint4*>(o.mp_desc)[2 * at + half] = v;
 }
 
-struct TlScratch {
-    DevBuf ws, io;
-    int device = -1;
-    void use_device(int dev) {
-        if (device != dev) {
-            ws.release();
-            io.release();
-            device = dev;
-        }
-    }
-};
-
 }  // namespace orbamd
 
 using namespace orbamd;
 
 namespace {
 
-thread_local TlScratch g_tl;
+thread_local Scratch g_tl;
 
 constexpr long long TL_MAX_ENTRIES = 0x7fffffffLL;
 
@@ -367,18 +355,14 @@ int tl_check(const orbtl_map* m, const orbtl_frames* fr, const orbtl_result* o) 
     return ORB_OK;
 }
 
+// CSR offsets and the keyframe slots they index
 int tl_check_csr(const int32_t* off, const int32_t* idx, int n, int range, const char* what) {
-    ORB_CHECK_ARG(off[0] == 0, std::string(what) + ": offsets must start at 0");
-    for (int i = 0; i < n; i++) ORB_CHECK_ARG(off[i + 1] >= off[i], std::string(what) + ": offsets must not decrease");
-    for (int e = 0; e < off[n]; e++)
-        ORB_CHECK_ARG(idx[e] >= 0 && idx[e] < range, std::string(what) + ": keyframe slot outside [0, n_keyframes)");
-    return ORB_OK;
+    int rc;
+    if ((rc = check_csr(off, n, 0x7fffffff, what))) return rc;
+    return check_range(idx, off[n], 0, range, (std::string(what) + ": keyframe slot outside [0, n_keyframes)").c_str());
 }
 
-int tl_check_slots(const int32_t* a, size_t n, int range, const char* msg) {
-    for (size_t i = 0; i < n; i++) ORB_CHECK_ARG(a[i] >= -1 && a[i] < range, msg);
-    return ORB_OK;
-}
+int tl_check_slots(const int32_t* a, size_t n, int range, const char* msg) { return check_range(a, n, -1, range, msg); }
 
 int tl_check_host(const orbtl_map* m, const orbtl_frames* fr) {
     const int K = m->n_keyframes, M = m->n_mappoints, F = fr->n_frames;
@@ -400,11 +384,6 @@ int tl_check_host(const orbtl_map* m, const orbtl_frames* fr) {
     return tl_check_slots(fr->frame_mappoint, (size_t)F * fr->kp_cap, M, "frame_mappoint entry outside [-1, n_mappoints)");
 }
 
-struct TlStage {   // bump allocation: measure, then place
-    size_t o = 0;
-    size_t take(size_t bytes) { const size_t r = o; o += align_up(std::max<size_t>(bytes, 1), 256); return r; }
-};
-
 }  // namespace
 
 extern "C" int orbtl_track_local_map_device(const orbtl_map* map, const orbtl_frames* frames, const orbtl_result* out,
@@ -412,23 +391,27 @@ extern "C" int orbtl_track_local_map_device(const orbtl_map* map, const orbtl_fr
     int rc;
     if ((rc = tl_check(map, frames, out))) return rc;
     if (frames->n_frames == 0) return ORB_OK;
-    int dev = 0;
-    ORB_HIP_TRY(hipGetDevice(&dev));
-    g_tl.use_device(dev);
+    if ((rc = g_tl.use_current_device())) return rc;
     hipStream_t st = (hipStream_t)stream;
     const orbtl_map& m = *map;
     const orbtl_frames& fr = *frames;
     const size_t F = fr.n_frames, K = m.n_keyframes, M = m.n_mappoints;
-    TlStage s;   // votes | mark | seen (zeroed together), first (all ones), cnt (written by tl_count_kernel)
-    const size_t o_votes = s.take(out->votes ? 0 : F * K * 4), o_mark = s.take(F * K), o_seen = s.take(F * M);
-    const size_t zero_end = s.o, o_first = s.take(F * M * 4), o_cnt = s.take(F * fr.kf_list_cap * 4);
-    if ((rc = g_tl.ws.reserve(s.o))) return rc;
+    TlWork w{};   // votes | mark | seen (zeroed together), first (all ones), cnt (written by tl_count_kernel)
+    size_t zero_end = 0;
+    auto carve = [&](char* base) {
+        Carver c{base};
+        c.take(w.votes, out->votes ? 0 : F * K); c.take(w.mark, F * K); c.take(w.seen, F * M);
+        zero_end = c.off;
+        c.take(w.first, F * M); c.take(w.cnt, F * fr.kf_list_cap);
+        return c.off;
+    };
+    if ((rc = g_tl.ws.reserve(carve(nullptr)))) return rc;
     char* p = g_tl.ws.as<char>();
-    TlWork w{out->votes ? out->votes : (int32_t*)(p + o_votes), (uint8_t*)(p + o_mark), (uint32_t*)(p + o_first),
-             (uint8_t*)(p + o_seen), (int32_t*)(p + o_cnt)};
+    carve(p);
+    if (out->votes) w.votes = out->votes;
     ORB_HIP_TRY(hipMemsetAsync(p, 0, zero_end, st));
     if (out->votes) ORB_HIP_TRY(hipMemsetAsync(out->votes, 0, std::max<size_t>(F * K * 4, 1), st));
-    ORB_HIP_TRY(hipMemsetAsync(p + o_first, 0xff, std::max<size_t>(F * M * 4, 1), st));
+    ORB_HIP_TRY(hipMemsetAsync(w.first, 0xff, std::max<size_t>(F * M * 4, 1), st));
     const unsigned nF = (unsigned)F, cap = (unsigned)fr.kf_list_cap;
     const unsigned per_frame = (unsigned)std::max(fr.kp_cap, fr.mp_cap);
     hipLaunchKernelGGL(tl_vote_kernel, dim3((fr.kp_cap + 255) / 256, nF), dim3(256), 0, st, m, fr, *out, w);
@@ -449,62 +432,26 @@ extern "C" int orbtl_track_local_map(const orbtl_map* map, const orbtl_frames* f
     if ((rc = tl_check(map, frames, out))) return rc;
     if (frames->n_frames == 0) return ORB_OK;
     if ((rc = tl_check_host(map, frames))) return rc;   // before any copy
-    ORB_HIP_TRY(hipSetDevice(device));
-    g_tl.use_device(device);
     const size_t F = frames->n_frames, K = map->n_keyframes, M = map->n_mappoints, kc = map->kf_cap, pc = frames->kp_cap,
                  lc = frames->kf_list_cap, mc = frames->mp_cap;
     const size_t n_child = K ? map->kf_child_off[K] : 0, n_obs = M ? map->mp_obs_off[M] : 0;
-    struct In { const void* src; size_t bytes; const void** dst; };
-    struct Out { void* host; size_t bytes; void** dst; };
     orbtl_map dm = *map;
     orbtl_frames df = *frames;
     orbtl_result dr = *out;
-    const orbtl_map& m_ = *map;
-    const orbtl_frames& f_ = *frames;
-    const In ins[] = {
-        {m_.kf_bad, K, (const void**)&dm.kf_bad}, {m_.kf_covis, K * TL_COVIS * 4, (const void**)&dm.kf_covis},
-        {m_.kf_parent, K * 4, (const void**)&dm.kf_parent}, {m_.kf_child_off, (K + 1) * 4, (const void**)&dm.kf_child_off},
-        {m_.kf_child_idx, n_child * 4, (const void**)&dm.kf_child_idx}, {m_.kf_n, K * 4, (const void**)&dm.kf_n},
-        {m_.kf_mappoint, K * kc * 4, (const void**)&dm.kf_mappoint}, {m_.mp_bad, M, (const void**)&dm.mp_bad},
-        {m_.mp_xw, M * 12, (const void**)&dm.mp_xw}, {m_.mp_normal, M * 12, (const void**)&dm.mp_normal},
-        {m_.mp_max_min, M * 8, (const void**)&dm.mp_max_min}, {m_.mp_desc, M * 32, (const void**)&dm.mp_desc},
-        {m_.mp_nobs, M * 4, (const void**)&dm.mp_nobs}, {m_.mp_obs_off, (M + 1) * 4, (const void**)&dm.mp_obs_off},
-        {m_.mp_obs_kf, n_obs * 4, (const void**)&dm.mp_obs_kf}, {m_.mp_visible, M * 4, (const void**)&dm.mp_visible},
-        {f_.frame_n, F * 4, (const void**)&df.frame_n}, {f_.frame_mappoint, F * pc * 4, (const void**)&df.frame_mappoint},
-        {f_.pose, F * 48, (const void**)&df.pose}, {f_.camera, F * 20, (const void**)&df.camera},
-        {f_.bounds, F * 16, (const void**)&df.bounds}, {f_.local_kf, F * lc * 4, (const void**)&df.local_kf},
-        {f_.n_local_kf, F * 4, (const void**)&df.n_local_kf}};
-    const Out outs[] = {
-        {out->reference_kf, F * 4, (void**)&dr.reference_kf}, {out->local_mp, F * mc * 4, (void**)&dr.local_mp},
-        {out->n_local_mp, F * 4, (void**)&dr.n_local_mp}, {out->n_to_match, F * 4, (void**)&dr.n_to_match},
-        {out->status, F * 4, (void**)&dr.status}, {out->kp_begin, (F + 1) * 4, (void**)&dr.kp_begin},
-        {out->mp_begin, (F + 1) * 4, (void**)&dr.mp_begin}, {out->kp_claimed, F * pc, (void**)&dr.kp_claimed},
-        {out->mp_valid, F * mc, (void**)&dr.mp_valid}, {out->mp_proj, F * mc * 12, (void**)&dr.mp_proj},
-        {out->mp_view_cos, F * mc * 4, (void**)&dr.mp_view_cos}, {out->mp_level, F * mc * 4, (void**)&dr.mp_level},
-        {out->mp_desc, F * mc * 32, (void**)&dr.mp_desc}, {out->mp_has_obs, F * mc, (void**)&dr.mp_has_obs},
-        {out->votes, out->votes ? F * K * 4 : 0, (void**)&dr.votes}};
-    TlStage s;
-    std::vector<size_t> at;
-    for (const In& i : ins) at.push_back(s.take(i.bytes));
-    for (const Out& o : outs) at.push_back(s.take(o.bytes));
-    if ((rc = g_tl.io.reserve(s.o))) return rc;
-    char* d = g_tl.io.as<char>();
-    size_t n = 0;
-    for (const In& i : ins) {
-        if (i.bytes) ORB_HIP_TRY(hipMemcpy(d + at[n], i.src, i.bytes, hipMemcpyHostToDevice));
-        *i.dst = d + at[n++];
-    }
-    for (const Out& o : outs) {
-        *o.dst = o.host ? d + at[n] : nullptr;
-        n++;
-    }
-    if ((rc = orbtl_track_local_map_device(&dm, &df, &dr, nullptr))) return rc;
-    ORB_HIP_TRY(hipStreamSynchronize(nullptr));
-    for (const Out& o : outs)
-        if (o.host && o.bytes) ORB_HIP_TRY(hipMemcpy(o.host, *o.dst, o.bytes, hipMemcpyDeviceToHost));
-    ORB_HIP_TRY(hipMemcpy(map->mp_visible, dm.mp_visible, M * 4, hipMemcpyDeviceToHost));
-    ORB_HIP_TRY(hipMemcpy(frames->frame_mappoint, df.frame_mappoint, F * pc * 4, hipMemcpyDeviceToHost));
-    ORB_HIP_TRY(hipMemcpy(frames->local_kf, df.local_kf, F * lc * 4, hipMemcpyDeviceToHost));
-    ORB_HIP_TRY(hipMemcpy(frames->n_local_kf, df.n_local_kf, F * 4, hipMemcpyDeviceToHost));
-    return ORB_OK;
+    Mirror io;
+    io.add(dm.kf_bad, K, true, false); io.add(dm.kf_covis, K * TL_COVIS, true, false); io.add(dm.kf_parent, K, true, false);
+    io.add(dm.kf_child_off, K + 1, true, false); io.add(dm.kf_child_idx, n_child, true, false); io.add(dm.kf_n, K, true, false);
+    io.add(dm.kf_mappoint, K * kc, true, false); io.add(dm.mp_bad, M, true, false); io.add(dm.mp_xw, M * 3, true, false);
+    io.add(dm.mp_normal, M * 3, true, false); io.add(dm.mp_max_min, M * 2, true, false); io.add(dm.mp_desc, M * 32, true, false);
+    io.add(dm.mp_nobs, M, true, false); io.add(dm.mp_obs_off, M + 1, true, false); io.add(dm.mp_obs_kf, n_obs, true, false);
+    io.add(dm.mp_visible, M, true, true);
+    io.add(df.frame_n, F, true, false); io.add(df.frame_mappoint, F * pc, true, true); io.add(df.pose, F * 12, true, false);
+    io.add(df.camera, F * 5, true, false); io.add(df.bounds, F * 4, true, false); io.add(df.local_kf, F * lc, true, true);
+    io.add(df.n_local_kf, F, true, true);
+    io.add(dr.reference_kf, F, false, true); io.add(dr.local_mp, F * mc, false, true); io.add(dr.n_local_mp, F, false, true);
+    io.add(dr.n_to_match, F, false, true); io.add(dr.status, F, false, true); io.add(dr.kp_begin, F + 1, false, true);
+    io.add(dr.mp_begin, F + 1, false, true); io.add(dr.kp_claimed, F * pc, false, true); io.add(dr.mp_valid, F * mc, false, true);
+    io.add(dr.mp_proj, F * mc * 3, false, true); io.add(dr.mp_view_cos, F * mc, false, true); io.add(dr.mp_level, F * mc, false, true);
+    io.add(dr.mp_desc, F * mc * 32, false, true); io.add(dr.mp_has_obs, F * mc, false, true); io.add(dr.votes, F * K, false, true);
+    return run_host(g_tl, device, io, [&] { return orbtl_track_local_map_device(&dm, &df, &dr, nullptr); });
 }

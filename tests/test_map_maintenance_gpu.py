@@ -153,6 +153,20 @@ def test_children_and_packed_tables_equal_the_restatement_and_feed_the_edge_list
     assert all(same(a, b) for a, b in zip(packed, built)) and len(packed[0]) > K
 
 
+def test_the_covis_host_entry_stages_in_the_shared_buffers_twice_around_another_entry():
+    """orbmm_covis_csr stages in the per-thread slab every host entry uses, and its device form keeps the query counts in
+    the workspace: two calls with UpdateConnections between them (which reuses both buffers) give the restatement."""
+    g = {k: MC.case("clean")[k] for k in R.STATE_KEYS}
+    queries = np.array([3, 0, 23], np.int32)
+    want = R.covis_csr(g, None, queries, append_self=True)
+    first = MM.CovisCsr(g, None, queries, append_self=True)
+    MM.UpdateConnections(MC.graph(MC.case("clean")), MC.BATCHES["five"])
+    second = MM.CovisCsr(g, None, queries, append_self=True)
+    for k in ("covis_begin", "covis_slot", "covis_weight", "conn_off", "conn_idx"):
+        assert same(first[k], want[k]) and same(second[k], want[k]), k
+    assert want["conn_off"][-1] > 3 and (want["conn_idx"][want["conn_off"][1:] - 1] == queries).all()
+
+
 def test_the_chain_on_one_stream_feeds_the_local_map():
     """UpdateConnections and UpdateNormalAndDepth, then TrackLocalMap reading the arrays they wrote, on one stream; the local
     point list differs from the one stale kf_covis / mp_normal give."""
