@@ -2004,6 +2004,133 @@ int orbmm_grow_observations(int32_t n_mappoints, int32_t n_obs, const int32_t* m
                             const int32_t* mp_obs_idx, int32_t slack, const int32_t* extra, int32_t n_obs_out,
                             int32_t* out_off, int32_t* out_kf, int32_t* out_idx, int32_t* status, int device);
 
+/* ------------------------------------------------------------------------------------------
+ * LoopCorrector::Correct (src/LoopClosing.cc:546-676), in place on the tables of orbmm_points / orbmm_graph: the
+ * connected list, the propagation of Scw to the current keyframe's neighbours with the correction of their map
+ * points and poses, and the LoopConnections sets; with orbba_essential_graph_edges_device the whole of CorrectLoop is
+ * stream-ordered: orbmm_update_connections_device(cur), orblc_connected_device, orblc_propagate_device,
+ * orbmm_update_connections_device(items), orbmm_fuse_apply_device (matched points), orbm_fuse_device /
+ * orbmm_fuse_apply_device per neighbour, orblc_loop_connections_device, orbmm_covis_csr_device,
+ * orbba_essential_graph_edges_device, orbba_optimize_essential_graph_device, orbmm_update_normal_depth_device.
+ * orblc_map carries the pointers of both structs and two tables of its own: mp_corrected_by (MapPoint::correctedByKF,
+ * a KeyFrame::id, initially 0) and mp_corrected_ref (correctedReference, as a slot).
+ * Departure: where the reference iterates a std::map<KeyFrame*, ...> (CorrectedSim3, LoopConnections) in pointer
+ * order, which no two runs share, the order here is ascending slot.
+ *
+ * orblc_connected (:550-552): connected[conn_cap + 1] = the ordered row of cur (ord_slot[cur][0 .. n_ord[cur])), a slot
+ * outside [0, n_keyframes) dropped, then cur itself, then -1; n_connected[0] = the count.  Every later entry takes
+ * `connected` in HBM and a host max_connected <= conn_cap + 1 (the entries it reads; -1 and a slot outside the table
+ * are skipped): n_connected read back, or conn_cap + 1, with identical results.
+ *
+ * orblc_propagate (:554-613 without UpdateConnections; csrc/lc_propagate.h): scw[13] = R row-major, t, s.
+ *   vertex_sim3 / edge_sim3 [K][13], the tables orbba_essential_graph takes: for a connected keyframe i the rows are
+ *   CorrectedSiw = Sim3(Tiw * Twc) * Scw (Scw for cur; Twc = kf_pose[cur].Inverse()) and NonCorrectedSiw = Sim3(Tiw);
+ *   for every other keyframe both are Sim3(kf_pose[k]), scale 1.  All rows from the poses as they are on entry, in
+ *   the reference's float CameraPose / Sim3 classes.
+ *   Claims: connected keyframes in ascending slot order, kf_mappoint[k][i] for i < kf_n[k] ascending; a point that is
+ *   null, outside its table, bad or has mp_corrected_by == kf_id[cur] is skipped, so each point is corrected once, by
+ *   the lowest connected slot that lists it, and a point that carries kf_id[cur] on entry by nobody.
+ *   A claimed point: mp_xw = (CorrectedSwi * Siw).Map(P) in float, mp_corrected_by = kf_id[cur], mp_corrected_ref = k,
+ *   then UpdateNormalAndDepth (orbmm_update_normal_depth's order and arithmetic) as the reference runs it inside the
+ *   walk: observer o, and the reference keyframe, contributes the camera centre of its corrected pose if it is
+ *   connected and o < k, of its entry pose otherwise.
+ *   kf_pose[k] of a connected keyframe becomes (R, (1. / s) * t) of CorrectedSiw, 1. / s and the product in double.
+ *   point_ref[M], the array orbba_essential_graph takes: -1 for a bad point, mp_corrected_ref where mp_corrected_by ==
+ *   kf_id[cur], else mp_ref_kf.
+ *   items (may be NULL) [max_connected]: the connected slots ascending, then -1: the batch the caller hands to
+ *   orbmm_update_connections_device behind this call (:612).
+ *   The claim is an integer atomicMin on a workspace array; no floating-point atomics: two runs are byte-identical.
+ *
+ * orblc_loop_connections (:661-676): for each connected[j] in list order, prev = its ordered row as it stands then,
+ * UpdateConnections on it, the set = its whole connection row minus prev minus every connected keyframe.  Output in
+ * the form orbba_eg_tables takes, rows in ascending slot order of conn_kf: conn_kf[max_connected] (an empty set keeps
+ * its row; the rows of skipped items come last with conn_kf = -1), conn_begin[max_connected + 1],
+ * conn_slot[max_connected * conn_cap] each list ascending (a stable compaction of the connection row, which is
+ * ascending), n_connections[0] = the rows that are not skipped.
+ * status[k] (written for every keyframe) is ORBMM_CONN_OVERFLOW if any of the updates reported it for k; such a
+ * keyframe keeps its rows, and its set comes from the unchanged row.  Three enqueues per item: a call made once
+ * per loop.
+ *
+ * Workspace per thread, grow-only: 76 bytes per keyframe and 4 per map point (propagate); 4 * (max_connected + 1) *
+ * (conn_cap + 3) + 4 * n_keyframes bytes (loop connections) besides orbmm_update_connections_device's own.
+ * ---------------------------------------------------------------------------------------- */
+typedef struct orblc_map {
+    int32_t n_keyframes, n_mappoints, kf_cap;
+    int32_t conn_cap;
+    int32_t n_obs;
+    int32_t n_levels;              /* 1 .. 32 */
+    const float*   scale_factors;  /* host memory, n_levels */
+    /* orbmm_graph's */
+    const int32_t* kf_id;          /* [K] */
+    const int32_t* kf_n;           /* [K] */
+    const int32_t* kf_mappoint;    /* [K][kf_cap] */
+    const uint8_t* mp_bad;         /* [M] */
+    const int32_t* mp_obs_off;     /* [M + 1] */
+    const int32_t* mp_obs_kf;
+    int32_t* conn_slot; int32_t* conn_weight; int32_t* n_conn;
+    int32_t* ord_slot;  int32_t* ord_weight;  int32_t* n_ord;
+    uint8_t* kf_first_connection;
+    int32_t* kf_parent;
+    int32_t* kf_covis;
+    int32_t* status;               /* [K] output of orblc_loop_connections */
+    /* orbmm_points' */
+    const int32_t* mp_obs_idx;
+    const int32_t* mp_ref_kf;      /* [M] */
+    const int32_t* kf_kp_octave;   /* [K][kf_cap] */
+    float* mp_xw;                  /* [M][3] updated in place */
+    float* kf_pose;                /* [K][12] updated in place */
+    float* mp_normal;              /* [M][3] updated in place */
+    float* mp_max_min;             /* [M][2] updated in place */
+    /* its own */
+    int32_t* mp_corrected_by;      /* [M] KeyFrame::id, initially 0 */
+    int32_t* mp_corrected_ref;     /* [M] slot */
+} orblc_map;
+
+/* The orbmm_graph that shares an orblc_map's arrays: what orbmm_update_connections[_device] takes for the same map. */
+static inline orbmm_graph orblc_graph(const orblc_map* m) {
+    orbmm_graph g;
+    g.n_keyframes = m->n_keyframes; g.n_mappoints = m->n_mappoints; g.kf_cap = m->kf_cap; g.conn_cap = m->conn_cap;
+    g.n_obs = m->n_obs; g.kf_id = m->kf_id; g.kf_n = m->kf_n; g.kf_mappoint = m->kf_mappoint; g.mp_bad = m->mp_bad;
+    g.mp_obs_off = m->mp_obs_off; g.mp_obs_kf = m->mp_obs_kf; g.conn_slot = m->conn_slot; g.conn_weight = m->conn_weight;
+    g.n_conn = m->n_conn; g.ord_slot = m->ord_slot; g.ord_weight = m->ord_weight; g.n_ord = m->n_ord;
+    g.kf_first_connection = m->kf_first_connection; g.kf_parent = m->kf_parent; g.kf_covis = m->kf_covis; g.status = m->status;
+    return g;
+}
+
+/* Device forms: every array in HBM but scale_factors; enqueue only on `stream`, nothing is copied back.  ORB_EINVAL
+ * for a NULL array the entry uses, negative sizes, kf_cap or conn_cap < 1, n_levels outside [1, 32], a table of 2^31
+ * entries or more, cur outside [0, n_keyframes), max_connected outside [0, conn_cap + 1].  orblc_connected reads the
+ * rows only; orblc_loop_connections what orbmm_update_connections reads and writes.  The workspace belongs to the
+ * calling thread: its calls must be stream-ordered. */
+int orblc_connected_device(const orblc_map* m, int32_t cur, int32_t* connected, int32_t* n_connected, void* stream);
+int orblc_propagate_device(const orblc_map* m, int32_t cur, const float* scw, const int32_t* connected,
+                           int32_t max_connected, float* vertex_sim3, float* edge_sim3, int32_t* point_ref,
+                           int32_t* items, void* stream);
+int orblc_loop_connections_device(const orblc_map* m, const int32_t* connected, int32_t max_connected, int32_t* conn_kf,
+                                  int32_t* conn_begin, int32_t* conn_slot, int32_t* n_connections, void* stream);
+/* Host forms: every pointer is host memory, synchronous; the updated arrays are written back.  Before anything is
+ * copied, besides the checks above, those of orbmm_update_connections / orbmm_update_normal_depth on the tables the
+ * entry uses, `connected` entries in [-1, n_keyframes), and for orblc_propagate a scale <= 0 and a non-finite scw. */
+int orblc_connected(const orblc_map* m, int32_t cur, int32_t* connected, int32_t* n_connected, int device);
+int orblc_propagate(const orblc_map* m, int32_t cur, const float* scw, const int32_t* connected, int32_t max_connected,
+                    float* vertex_sim3, float* edge_sim3, int32_t* point_ref, int32_t* items, int device);
+int orblc_loop_connections(const orblc_map* m, const int32_t* connected, int32_t max_connected, int32_t* conn_kf,
+                           int32_t* conn_begin, int32_t* conn_slot, int32_t* n_connections, int device);
+
+/* orbba_essential_graph_edges on the device: every array of g, edge_i, edge_j, edge_table and n_edges in HBM; the
+ * counts are host integers: n_loop_slots, n_covis_slots and n_conn_slots are the entries of loop_slot, covis_slot /
+ * covis_weight and conn_slot (an offset read from the device is clamped to them).  g->n_connections may be the row
+ * capacity: a row with conn_kf = -1 is skipped.  The loop connections are listed by one workgroup (a scan per row);
+ * then per keyframe count, scan, fill, the insertedEdges test a search of the kept loop-connection pairs in either
+ * direction.  edge_i / edge_j / edge_table are written up to `capacity`, the entries from the count up to capacity
+ * as (-1, -1, 0), which orbba_optimize_essential_graph_device leaves out of the graph (so it can be called with
+ * n_edges = capacity and nothing read back); n_edges[0] = the full count.  An index read from device memory outside
+ * its table is skipped.  ORB_EINVAL for null pointers, n_keyframes < 1, negative sizes, curr_slot / loop_kf_slot out
+ * of range. */
+int orbba_essential_graph_edges_device(const orbba_eg_tables* g, int32_t n_loop_slots, int32_t n_covis_slots,
+                                       int32_t n_conn_slots, int32_t min_weight, int32_t capacity, int32_t* edge_i,
+                                       int32_t* edge_j, uint8_t* edge_table, int32_t* n_edges, void* stream);
+
 const char* orb_last_error(void);
 int orb_device_count(void);
 

@@ -952,6 +952,44 @@ private:
     orbmm_observe tables_;
 };
 
+// LoopCorrector::Correct (src/LoopClosing.cc:546-676): the host owns the arrays of orblc_map in HBM and enqueues the steps
+// on one stream; nothing is copied back.  The fuse steps between Propagate and LoopConnections are Observations' and
+// ORBmatcher's.
+class LoopCorrection {
+public:
+    explicit LoopCorrection(const orblc_map& map) : map_(map) {}
+    // connectedKFs (:550-552): d_connected holds conn_cap + 1 entries, d_n_connected one
+    void Connected(int32_t cur, int32_t* d_connected, int32_t* d_n_connected, void* stream = nullptr) const {
+        check(orblc_connected_device(&map_, cur, d_connected, d_n_connected, stream), "orblc_connected_device");
+    }
+    // :554-613: the propagation, then UpdateConnections of the connected keyframes in ascending slot order (d_items,
+    // max_connected entries, is filled by the first call and read by the second)
+    void Propagate(int32_t cur, const float* d_scw, const int32_t* d_connected, int32_t max_connected, float* d_vertex_sim3,
+                   float* d_edge_sim3, int32_t* d_point_ref, int32_t* d_items, void* stream = nullptr) const {
+        check(orblc_propagate_device(&map_, cur, d_scw, d_connected, max_connected, d_vertex_sim3, d_edge_sim3, d_point_ref, d_items,
+                                     stream), "orblc_propagate_device");
+        const orbmm_graph g = orblc_graph(&map_);
+        check(orbmm_update_connections_device(&g, max_connected, d_items, stream), "orbmm_update_connections_device");
+    }
+    // :661-676: the LoopConnections sets in orbba_eg_tables' form
+    void LoopConnections(const int32_t* d_connected, int32_t max_connected, int32_t* d_conn_kf, int32_t* d_conn_begin,
+                         int32_t* d_conn_slot, int32_t* d_n_connections, void* stream = nullptr) const {
+        check(orblc_loop_connections_device(&map_, d_connected, max_connected, d_conn_kf, d_conn_begin, d_conn_slot, d_n_connections,
+                                            stream), "orblc_loop_connections_device");
+    }
+    // Optimizer.cc:798-903 on the device; the lists past the count are (-1, -1, 0)
+    static void EssentialGraphEdges(const orbba_eg_tables& tables, int32_t n_loop_slots, int32_t n_covis_slots, int32_t n_conn_slots,
+                                    int32_t min_weight, int32_t capacity, int32_t* d_edge_i, int32_t* d_edge_j,
+                                    uint8_t* d_edge_table, int32_t* d_n_edges, void* stream = nullptr) {
+        check(orbba_essential_graph_edges_device(&tables, n_loop_slots, n_covis_slots, n_conn_slots, min_weight, capacity, d_edge_i,
+                                                 d_edge_j, d_edge_table, d_n_edges, stream), "orbba_essential_graph_edges_device");
+    }
+    const orblc_map& map() const { return map_; }
+
+private:
+    orblc_map map_;
+};
+
 }  // namespace ORB_SLAM2_AMD
 
 #endif  // ORBSLAM2_AMD_HPP

@@ -28,6 +28,8 @@ Host mirrors of the reference's interfaces (tiantianxuabc/ORB_SLAM2_Refactored):
   AddKeyFrameObservations / FuseApply <- MapPoint::AddObservation and Replace (src/MapPoint.cc:109-122, 191-230) under
                                      ProcessNewKeyFrame's loop, Fuse's apply loops and CorrectLoop's matched points, with
                                      GrowObservations, observations.py
+  Connected / Propagate / LoopConnections <- LoopCorrector::Correct (src/LoopClosing.cc:546-676) and the edge list of
+                                     OptimizeEssentialGraph on the device, loop_correction.py
 All compute runs in liborbslam2_amd.so (HIP kernels behind include/orbslam2_amd.h).
 """
 from .extractor import ORBextractor, KP_DTYPE

@@ -366,6 +366,16 @@ class OrbmmCsr(C.Structure):
                 ("conn_off", C.c_void_p), ("conn_idx", C.c_void_p)]
 
 
+class OrblcMap(C.Structure):
+    """orblc_map (include/orbslam2_amd.h)."""
+    _fields_ = [("n_keyframes", C.c_int32), ("n_mappoints", C.c_int32), ("kf_cap", C.c_int32), ("conn_cap", C.c_int32),
+                ("n_obs", C.c_int32), ("n_levels", C.c_int32)] + [
+        (k, C.c_void_p) for k in ("scale_factors", "kf_id", "kf_n", "kf_mappoint", "mp_bad", "mp_obs_off", "mp_obs_kf", "conn_slot",
+                                  "conn_weight", "n_conn", "ord_slot", "ord_weight", "n_ord", "kf_first_connection", "kf_parent",
+                                  "kf_covis", "status", "mp_obs_idx", "mp_ref_kf", "kf_kp_octave", "mp_xw", "kf_pose", "mp_normal",
+                                  "mp_max_min", "mp_corrected_by", "mp_corrected_ref")]
+
+
 class OrbmmCull(C.Structure):
     """orbmm_cull (include/orbslam2_amd.h)."""
     _fields_ = [("n_keyframes", C.c_int32), ("n_mappoints", C.c_int32), ("kf_cap", C.c_int32), ("conn_cap", C.c_int32),
@@ -498,6 +508,14 @@ SIGNATURES = {    "orbx_create": (C.c_int, [C.POINTER(OrbxParams), C.c_int, C.PO
     "orbmm_fuse_apply": (C.c_int, [C.POINTER(OrbmmObserve), C.POINTER(OrbmmApply), C.c_int]),
     "orbmm_grow_observations_device": (C.c_int, [C.c_int32, C.c_int32, VP, VP, VP, C.c_int32, VP, C.c_int32, VP, VP, VP, VP, VP]),
     "orbmm_grow_observations": (C.c_int, [C.c_int32, C.c_int32, VP, VP, VP, C.c_int32, VP, C.c_int32, VP, VP, VP, VP, C.c_int]),
+    "orblc_connected_device": (C.c_int, [C.POINTER(OrblcMap), C.c_int32, VP, VP, VP]),
+    "orblc_connected": (C.c_int, [C.POINTER(OrblcMap), C.c_int32, VP, VP, C.c_int]),
+    "orblc_propagate_device": (C.c_int, [C.POINTER(OrblcMap), C.c_int32, VP, VP, C.c_int32, VP, VP, VP, VP, VP]),
+    "orblc_propagate": (C.c_int, [C.POINTER(OrblcMap), C.c_int32, VP, VP, C.c_int32, VP, VP, VP, VP, C.c_int]),
+    "orblc_loop_connections_device": (C.c_int, [C.POINTER(OrblcMap), VP, C.c_int32, VP, VP, VP, VP, VP]),
+    "orblc_loop_connections": (C.c_int, [C.POINTER(OrblcMap), VP, C.c_int32, VP, VP, VP, VP, C.c_int]),
+    "orbba_essential_graph_edges_device": (C.c_int, [C.POINTER(EssentialGraphTables), C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                                     C.c_int32, VP, VP, VP, VP, VP]),
     "orbx_pack_descriptors": (C.c_int,[VP, C.c_int, VP, VP, C.c_int, VP, C.c_int, VP]),
     "orbx_profile_enable": (C.c_int, [VP, C.c_int]),
     "orbx_profile_read": (C.c_int, [VP, VP, VP]),

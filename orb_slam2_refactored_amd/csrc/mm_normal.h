@@ -49,8 +49,16 @@ MM_HD void mm_center(const float* pose, float* Ow) {
     }
 }
 
-// Returns true when the point's normal and distances were written.
-MM_HD bool mm_update_point(const MmPoints& t, int p) {
+// The camera centre an observer contributes: center(k) points at three floats.  MmTableCenter is kf_ow's row.
+struct MmTableCenter {
+    const float* ow;
+    MM_HD const float* operator()(int k) const { return ow + 3 * (size_t)k; }
+};
+
+// Returns true when the point's normal and distances were written.  The centre of every observer, and of the reference
+// keyframe, is center(slot): lc_propagate.h selects between two tables per observer.
+template <class Center>
+MM_HD bool mm_update_point_at(const MmPoints& t, int p, const Center& center) {
     if (p < 0 || p >= t.M || t.mp_bad[p]) return false;
     const int ref = t.mp_ref_kf[p];
     if (ref < 0 || ref >= t.K) return false;
@@ -64,7 +72,7 @@ MM_HD bool mm_update_point(const MmPoints& t, int p) {
     for (int e = e0; e < e1; e++) {
         const int k = t.mp_obs_kf[e];
         if (k < 0 || k >= t.K) continue;
-        const float* Ow = t.kf_ow + 3 * (size_t)k;
+        const float* Ow = center(k);
         const float d[3] = {X[0] - Ow[0], X[1] - Ow[1], X[2] - Ow[2]};
         const double inv = 1. / norm3d(d[0], d[1], d[2]);
         for (int i = 0; i < 3; i++) sum[i] += (float)(inv * (double)d[i]);
@@ -80,7 +88,7 @@ MM_HD bool mm_update_point(const MmPoints& t, int p) {
     if (ref_idx < 0 || ref_idx >= lim) return false;
     const int octave = t.kf_kp_octave[(size_t)ref * t.kf_cap + ref_idx];
     if (octave < 0 || octave >= t.n_levels) return false;
-    const float* Or = t.kf_ow + 3 * (size_t)ref;
+    const float* Or = center(ref);
     const float dist = lm_norm3(X[0] - Or[0], X[1] - Or[1], X[2] - Or[2]);
     const float max_distance = t.scale[octave] * dist;
     t.mp_max_min[2 * (size_t)p] = max_distance;
@@ -89,5 +97,7 @@ MM_HD bool mm_update_point(const MmPoints& t, int p) {
     for (int i = 0; i < 3; i++) t.mp_normal[3 * (size_t)p + i] = (float)((double)sum[i] * inv_n);
     return true;
 }
+
+MM_HD bool mm_update_point(const MmPoints& t, int p) { return mm_update_point_at(t, p, MmTableCenter{t.kf_ow}); }
 
 }  // namespace orbamd
