@@ -291,7 +291,10 @@ int orbm_search_by_bow_kf_batch_device(const orbm_bow_batch* b, int32_t* d_match
  * A view is one frame: its keypoints (level-0 coordinates, cv::KeyPoint layout), descriptors and
  * unblurred pyramid levels (GetImagePyramid()).  The right keypoints' row table (vRowIndices) is
  * built on the device for images of at most 4096 rows (ORB_EINVAL above); a row band reaching past
- * the image is clipped to it (the reference indexes outside vRowIndices there). */
+ * the image is clipped to it (the reference indexes outside vRowIndices there).  At most 12286
+ * keypoints per side and frame (slots, for the device entries), ORB_EINVAL above.  Not checked, as
+ * in the reference: the left 11x11 patch and the right window from column suR - 10 on must lie inside
+ * the left octave's level for every candidate below the Hamming gate. */
 typedef struct orbm_stereo_view {
     int32_t n;
     const orbx_keypoint* kps;

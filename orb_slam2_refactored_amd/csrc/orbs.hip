@@ -218,7 +218,12 @@ __global__ __launch_bounds__(256) void stereo_match_kernel(StereoSide L, StereoS
 
 // Median-distance filter (:229-246): m = max(n/2 - 1, 0) over the matched SAD distances sorted
 // descending; every match with dist >= 1.5f*1.4f*median is dropped.  n == 0: nothing (the
-// reference indexes an empty vector there).
+// reference indexes an empty vector there).  A frame's SADs sit in dynamic LDS (cap ints) behind the two
+// static ints; launch_stereo keeps the sum within ST_FILTER_LDS, the 48 KiB every launch here stays
+// under unless hipFuncAttributeMaxDynamicSharedMemorySize was raised for its kernel (as orbx.hip does
+// for the quadtree kernels).  It is not raised for this one.
+constexpr size_t ST_FILTER_LDS = 48 * 1024, ST_FILTER_STATIC_LDS = 2 * sizeof(int);
+constexpr int ST_MAX_CAP = (int)((ST_FILTER_LDS - ST_FILTER_STATIC_LDS) / sizeof(int));   // 12286
 __global__ __launch_bounds__(256) void stereo_filter_kernel(const int32_t* __restrict__ cntL, int nLf, int cap,
                                                             float* __restrict__ uright, float* __restrict__ depth,
                                                             const int32_t* __restrict__ sad) {
@@ -279,7 +284,8 @@ int launch_stereo(const StereoSide& L, const StereoSide& R, const StereoParams& 
                   const orbx_keypoint* kpsR, const uint8_t* descR, const int32_t* cntR, int nR_fixed, int cap,
                   float* uright, float* depth, int32_t* scratch, hipStream_t st) {
     if (n_frames <= 0 || cap <= 0) return ORB_OK;
-    ORB_CHECK_ARG(cap <= 65535, "stereo: cap too large");
+    static_assert(ST_MAX_CAP <= 65535, "stereo_match_kernel packs the right index into 16 bits");
+    ORB_CHECK_ARG(cap <= ST_MAX_CAP, "stereo: more than 12286 keypoints per frame (the median filter's LDS)");
     ORB_CHECK_ARG(L.rows[0] > 0 && L.rows[0] <= ST_MAX_ROWS, "stereo: image rows must be 1..4096");
     const int span = stereo_row_span(sp, L.nlevels);
     int32_t* sad = scratch;
