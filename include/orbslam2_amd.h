@@ -2172,6 +2172,19 @@ int orbx_debug_qt_sort(const int32_t* sizes, int n, int32_t* perm);
 int orbba_debug_po_wave(const double* in, double* scatter, double* sum);
 /* Quadtree output of (frame, level) of the last batch (list order, packed as above). */
 int orbx_debug_level_selected(const orbx_extractor* h, int frame, int level, uint32_t* out, int cap, int* n);
+/* describe alone, on planted keypoints.  imgs: n_frames host frames of rows x cols, rows `step` bytes apart,
+ * frame f at imgs + f * rows * step.  points: n planted keypoints as int32 (level, x, y, score), x / y in
+ * level coordinates; every frame gets the same points.  The pyramid is built as Extract builds it (same
+ * kernels, same handle switches), the points are written as the quadtree's selection words and per-level
+ * counts (in the given order within a level), and describe_prefix_kernel plus the describe launch the handle
+ * is configured for run on them (slot table, ORBX_DESC_DENSE, ORBX_DESC_C with the overflow kernel; the
+ * trig mode of orbx_set_opencv_compat).  kps / desc receive n_frames x n records / 32-byte descriptors:
+ * per frame level-major, then plant order.  ORB_EINVAL, before anything is launched, for a level outside
+ * [0, nlevels) or one that takes no keypoints, x outside [19, w - 19) or y outside [19, h - 19) of the
+ * level (FAST's range: a planted point reads nothing Extract could not reach), a score outside 0..255, or
+ * more points on a level than its selection capacity (the level's share of orbx_max_keypoints). */
+int orbx_debug_describe(orbx_extractor* h, const uint8_t* imgs, int n_frames, int rows, int cols, size_t step,
+                        const int32_t* points, int n, orbx_keypoint* kps, uint8_t* desc);
 
 #ifdef __cplusplus
 }

@@ -1612,6 +1612,36 @@ int oracle_extract(const orbx_params* prm, const uint8_t* img, int rows, int col
     return 0;
 }
 
+// describe alone on planted keypoints: points = n x (level, x, y, score) in level coordinates.  The pyramid,
+// IC_Angle on the raw level, one blur per level that has points, the descriptor, and the record as extract()
+// writes it (response = the planted score); output level-major, then plant order.  ORB_EINVAL for a point
+// outside what DetectFAST can return ([19, w - 19) x [19, h - 19) of its level).
+int oracle_describe(const orbx_params* prm, const uint8_t* img, int rows, int cols, size_t step, const int32_t* points,
+                    int n, orbx_keypoint* kps, uint8_t* desc) {
+    Extractor ex(to_params(prm));
+    ex.pyramid(view(img, rows, cols, step));
+    for (int i = 0; i < n; i++) {
+        const int l = points[4 * i], x = points[4 * i + 1], y = points[4 * i + 2], s = points[4 * i + 3];
+        if (l < 0 || l >= prm->nlevels || s < 0 || s > 255) return ORB_EINVAL;
+        const Img& im = ex.levels[l];
+        if (x < 19 || x >= im.cols - 19 || y < 19 || y >= im.rows - 19) return ORB_EINVAL;
+    }
+    int o = 0;
+    for (int l = 0; l < prm->nlevels; l++) {
+        Img blurred;
+        for (int i = 0; i < n; i++) {
+            if (points[4 * i] != l) continue;
+            if (!blurred.rows) gaussian_blur(ex.levels[l], blurred);
+            Kp k{(float)points[4 * i + 1], (float)points[4 * i + 2], ex.scale[l] * 31, -1.f, (float)points[4 * i + 3], l};
+            k.angle = ex.ic_angle(ex.levels[l], k.x, k.y);
+            Extractor::describe(k, blurred, desc + (size_t)o * 32);
+            if (l > 0) { k.x *= ex.scale[l]; k.y *= ex.scale[l]; }
+            to_abi(k, &kps[o++]);
+        }
+    }
+    return 0;
+}
+
 int oracle_descriptor_distance(const uint8_t* a, const uint8_t* b) { return hamming(a, b); }
 
 // Best / second-best scan (ORBmatcher.cc:477-498) + acceptance (:500).

@@ -523,6 +523,7 @@ SIGNATURES = {    "orbx_create": (C.c_int, [C.POINTER(OrbxParams), C.c_int, C.PO
     "orbx_debug_qt_sort": (C.c_int, [VP, C.c_int, VP]),
     "orbba_debug_po_wave": (C.c_int, [VP, VP, VP]),
     "orbx_debug_level_selected": (C.c_int, [VP, C.c_int, C.c_int, VP, C.c_int, C.POINTER(C.c_int)]),
+    "orbx_debug_describe": (C.c_int, [VP, VP, C.c_int, C.c_int, C.c_int, SZ, VP, C.c_int, VP, VP]),
     "orb_last_error": (C.c_char_p, []),
     "orb_device_count": (C.c_int, []),
 }

@@ -551,10 +551,11 @@ static auto fast_kernel_for(const FastLds& fl, bool pair) -> decltype(&fast_cell
 
 // All four stages for frames [f0, f0 + F) of the workspace, enqueued on st.  Every kernel indexes
 // its per-frame buffers from the frame index within the launch, so a chunk is launched with base
-// pointers advanced by f0 frames.
+// pointers advanced by f0 frames.  planted (orbx_debug_describe): the selection words and counts are already
+// in d_sel / d_selcnt, so FAST and the quadtree are left out; the pyramid and describe launches are the same.
 static void launch_chunk(orbx_extractor* h, int f0, const uint8_t* d_imgs, int F, long long fstride, int step,
                          orbx_keypoint* d_kps, uint8_t* d_desc, int32_t* d_counts, int cap, hipStream_t st,
-                         hipStream_t side = nullptr) {
+                         hipStream_t side = nullptr, bool planted = false) {
     const Geom& g = h->geom;
     uint8_t* pyr = h->d_pyr.as<uint8_t>() + (long long)f0 * g.pyr_frame_bytes;
     d_imgs += (long long)f0 * fstride;
@@ -623,7 +624,7 @@ static void launch_chunk(orbx_extractor* h, int f0, const uint8_t* d_imgs, int F
         return 0;
     };
     const int nc0 = g.lv[0].ncells;
-    if (side && nc0 > 0 && g.nlevels > 1) {
+    if (side && nc0 > 0 && g.nlevels > 1 && !planted) {
         // Level 0 needs no pyramid: its FAST + quadtree run on the side stream while the main
         // stream builds levels 1..7 (latency-bound cascade) and runs their FAST / quadtree, so the
         // level-0 tree's serial rounds overlap the FAST work of the other levels.
@@ -641,8 +642,10 @@ static void launch_chunk(orbx_extractor* h, int f0, const uint8_t* d_imgs, int F
         {
             for (int l = 1; l < g.nlevels; l++) l += pyramid(l);
         }
-        fast(0, g.nlevels, st);
-        quadtree(0, g.nlevels, st);
+        if (!planted) {
+            fast(0, g.nlevels, st);
+            quadtree(0, g.nlevels, st);
+        }
     }
     int* lvlpre = h->d_lvlpre.as<int>() + (long long)f0 * LVP;
     hipLaunchKernelGGL(describe_prefix_kernel, dim3((unsigned)((F + 255) / 256)), dim3(256), 0, st, (const int*)selcnt,
@@ -1079,6 +1082,71 @@ int orbx_debug_level_selected(const orbx_extractor* h, int frame, int level, uin
         ORB_HIP_TRY(hipMemcpy(out, h->d_sel.as<uint32_t>() + (long long)frame * g.out_frame + g.lv[level].out_base,
                               4 * (size_t)std::min(c, cap), hipMemcpyDeviceToHost));
     return ORB_OK;
+}
+
+int orbx_debug_describe(orbx_extractor* h, const uint8_t* imgs, int n_frames, int rows, int cols, size_t step,
+                        const int32_t* points, int n, orbx_keypoint* kps, uint8_t* desc) {
+    ORB_CHECK_ARG(h && imgs && points && kps && desc, "null argument");
+    ORB_CHECK_ARG(n_frames >= 1 && n_frames <= 65535 && n >= 1, "bad frame / point count");
+    ORB_CHECK_ARG(rows > 0 && cols > 0 && step >= (size_t)cols, "frames must be non-empty CV_8U matrices");
+    std::lock_guard<std::mutex> lk(h->mu);
+    ORB_HIP_TRY(hipSetDevice(h->device));
+    int rc = setup_geometry(h, rows, cols);
+    if (rc) return rc;
+    const Geom& g = h->geom;
+    // the planted selection of one frame (level-major, plant order inside a level): every point inside
+    // what FAST can return, so describe reads nothing Extract could not reach
+    std::vector<uint32_t> sel1((size_t)g.out_frame, 0u);
+    std::vector<int> cnt1((size_t)g.nlevels, 0);
+    for (int i = 0; i < n; i++) {
+        const int l = points[4 * i], x = points[4 * i + 1], y = points[4 * i + 2], s = points[4 * i + 3];
+        ORB_CHECK_ARG(l >= 0 && l < g.nlevels, "planted point: level outside [0, nlevels)");
+        const LevelDev& L = g.lv[l];
+        ORB_CHECK_ARG(L.out_cap > 0, "planted point: the level takes no keypoints");
+        ORB_CHECK_ARG(x >= 19 && x < L.w - 19 && y >= 19 && y < L.h - 19, "planted point outside [19, w - 19) x [19, h - 19)");
+        ORB_CHECK_ARG(s >= 0 && s <= 255, "planted point: score outside 0..255");
+        ORB_CHECK_ARG(cnt1[l] < L.out_cap, "more planted points on a level than its selection capacity");
+        sel1[(size_t)L.out_base + cnt1[l]++] = (uint32_t)x | ((uint32_t)y << 12) | ((uint32_t)s << 24);
+    }
+    const int F = n_frames, kcap = max_keypoints(g);
+    if ((rc = reserve_workspace(h, F))) return rc;
+    if ((rc = h->d_img.reserve((size_t)F * rows * cols))) return rc;
+    if ((rc = h->d_kps.reserve((size_t)F * kcap * sizeof(orbx_keypoint)))) return rc;
+    if ((rc = h->d_desc.reserve((size_t)F * kcap * 32))) return rc;
+    if ((rc = h->d_counts.reserve(std::max<size_t>(16, (size_t)F * 4)))) return rc;
+    hipStream_t st = h->stream;
+    const long long fstride = (long long)rows * cols;
+    // frames are rows * step bytes apart: F * rows rows of one pitched copy (tight on the device, as orbx_extract)
+    if (step == (size_t)cols)
+        ORB_HIP_TRY(hipMemcpyAsync(h->d_img.ptr, imgs, (size_t)F * rows * cols, hipMemcpyHostToDevice, st));
+    else
+        ORB_HIP_TRY(hipMemcpy2DAsync(h->d_img.ptr, cols, imgs, step, cols, (size_t)F * rows, hipMemcpyHostToDevice, st));
+    std::vector<uint32_t> sel((size_t)F * g.out_frame);
+    std::vector<int> cnt((size_t)F * g.nlevels);
+    for (int f = 0; f < F; f++) {
+        std::copy(sel1.begin(), sel1.end(), sel.begin() + (size_t)f * g.out_frame);
+        std::copy(cnt1.begin(), cnt1.end(), cnt.begin() + (size_t)f * g.nlevels);
+    }
+    ORB_HIP_TRY(hipMemcpyAsync(h->d_sel.ptr, sel.data(), sel.size() * 4, hipMemcpyHostToDevice, st));
+    ORB_HIP_TRY(hipMemcpyAsync(h->d_selcnt.ptr, cnt.data(), cnt.size() * 4, hipMemcpyHostToDevice, st));
+    h->last_in = h->d_img.as<uint8_t>();
+    h->last_fstride = fstride;
+    h->last_step = cols;
+    h->last_frames = F;
+    h->last_single = false;
+    if ((rc = describe_grid_begin(h, st))) return rc;
+    launch_chunk(h, 0, h->d_img.as<uint8_t>(), F, fstride, cols, h->d_kps.as<orbx_keypoint>(), h->d_desc.as<uint8_t>(),
+                 h->d_counts.as<int32_t>(), kcap, st, nullptr, true);
+    ORB_HIP_TRY(hipGetLastError());
+    if ((rc = describe_grid_end(h, st))) return rc;
+    for (int f = 0; f < F; f++) {   // the frame's first n rows: level-major, plant order
+        ORB_HIP_TRY(hipMemcpyAsync(kps + (size_t)f * n, h->d_kps.as<orbx_keypoint>() + (size_t)f * kcap,
+                                   (size_t)n * sizeof(orbx_keypoint), hipMemcpyDeviceToHost, st));
+        ORB_HIP_TRY(hipMemcpyAsync(desc + (size_t)f * n * 32, h->d_desc.as<uint8_t>() + (size_t)f * kcap * 32, (size_t)n * 32,
+                                   hipMemcpyDeviceToHost, st));
+    }
+    ORB_HIP_TRY(hipStreamSynchronize(st));
+    return check_fault(h);
 }
 
 int orbx_profile_enable(orbx_extractor* h, int enable) {

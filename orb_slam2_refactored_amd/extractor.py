@@ -151,6 +151,31 @@ class ORBextractor:
         a = a[:n.value]
         return np.stack([a & 0xfff, (a >> 12) & 0xfff, a >> 24], axis=1).astype(np.int32)
 
+    def debug_describe(self, frames, points):
+        """describe alone on planted keypoints (orbx_debug_describe): frames uint8 [F, H, W] (or one
+        [H, W] image), points int32 [n, 4] = (level, x, y, score) in level coordinates, planted in every
+        frame.  Returns (keypoints [F, n] KP_DTYPE, descriptors [F, n, 32]), per frame level-major and then
+        in plant order ([n] / [n, 32] for a single image).  Raises OrbError for a point Extract could not
+        produce (include/orbslam2_amd.h)."""
+        fr = np.asarray(frames)
+        single = fr.ndim == 2
+        if single:
+            fr = fr[None]
+        if fr.dtype != np.uint8 or fr.ndim != 3:
+            raise ValueError("frames must be CV_8U [F, H, W] or [H, W]")
+        fr = np.ascontiguousarray(fr)
+        pts = np.ascontiguousarray(points, dtype=np.int32)
+        if pts.ndim != 2 or pts.shape[1] != 4 or len(pts) == 0:
+            raise ValueError("points must be int32 [n, 4] = (level, x, y, score), n >= 1")
+        F, rows, cols = fr.shape
+        n = len(pts)
+        kps = np.zeros((F, n), KP_DTYPE)
+        desc = np.zeros((F, n, 32), np.uint8)
+        check(lib().orbx_debug_describe(self._h, ptr(fr), F, rows, cols, C.c_size_t(cols), ptr(pts), n, ptr(kps),
+                                        ptr(desc)), "orbx_debug_describe")
+        self._last_shape = (rows, cols)
+        return (kps[0], desc[0]) if single else (kps, desc)
+
     # -- batched, HBM-resident mode (torch tensors on the GPU)
     def extract_batch_device(self, frames, kps_out=None, desc_out=None, counts_out=None, stream=None):
         """frames: uint8 CUDA tensor [F, H, W].  Returns (kps [F,cap,28B] as int32 view, desc [F,cap,32],

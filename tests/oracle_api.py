@@ -174,6 +174,25 @@ def extract(p, img, cap=8192):
     return kps[:n.value].copy(), desc[:n.value].copy(), per
 
 
+def describe(p, img, points):
+    """describe alone on planted keypoints (oracle_describe): points int32 [n, 4] = (level, x, y, score)
+    in level coordinates.  Returns (keypoints, descriptors), level-major and then in plant order."""
+    img = np.ascontiguousarray(img)
+    pts = np.ascontiguousarray(points, dtype=np.int32).reshape(-1, 4)
+    kps = np.zeros(len(pts), KP_DTYPE)
+    desc = np.zeros((len(pts), 32), np.uint8)
+    rc = lib().oracle_describe(C.byref(p), ptr(img), img.shape[0], img.shape[1], C.c_size_t(img.shape[1]), ptr(pts),
+                               len(pts), ptr(kps), ptr(desc))
+    if rc != 0:
+        raise ValueError(f"oracle_describe: planted point outside what DetectFAST can return (rc {rc})")
+    return kps, desc
+
+
+def fast_atan2(y, x):
+    """cv::fastAtan2 as the oracle restates it (degrees, float32)."""
+    return np.float32(lib().oracle_fast_atan2(C.c_float(y), C.c_float(x)))
+
+
 def bf_match(A, B, nnratio=0.6, th_low=50):
     A = np.ascontiguousarray(A, np.uint8)
     B = np.ascontiguousarray(B, np.uint8)
