@@ -746,6 +746,135 @@ int orbba_local_ba(const orbba_problem* prob, orbba_result* res, const volatile 
                    int device);
 
 /* ------------------------------------------------------------------------------------------
+ * Optimizer::LocalBundleAdjustment(currKF, stopFlag, map) as a whole (src/Optimizer.cc:491-736), in place on the slot
+ * tables of the map-maintenance entries below (orbtl_map's conventions: a slot stands for a pointer, -1 is null; a
+ * slot, an offset or an index read from device memory is not trusted: one outside its table is skipped and no store
+ * leaves a table).  Three parts, each with an entry of its own (csrc/ba_window.h holds the rules):
+ *
+ * 1. The window (:493-631), orbba_local_window.  In orbba_problem's order:
+ *    local keyframes  cur, then ord_slot[cur][0 .. n_ord[cur]) in row order without those whose kf_bad is set (a bad
+ *                     neighbour still counts as marked BALocalForKF: it is never a fixed camera); a neighbour equal to
+ *                     cur or met before in the row is skipped.
+ *    local points     the local keyframes in list order, kf_mappoint[k][0 .. kf_n[k]) in index order: each point that
+ *                     is not null and not bad, at its first occurrence.
+ *    fixed cameras    the local points in list order, their observations in CSR order without the erased ones
+ *                     (mp_obs_kf == -1): each keyframe neither marked local nor marked fixed, at its first occurrence;
+ *                     a bad keyframe is marked but not listed.  Departure, the one UpdateNormalAndDepth and the culls
+ *                     make: the reference walks a std::map<KeyFrame*, size_t> in pointer order; here it is CSR order.
+ *    edges            point-major in local-point order; a point's observations in CSR order without erased entries and
+ *                     bad keyframes (and without an observation whose keypoint index or octave is outside its table).
+ *                     Per edge: edge_point, edge_pose (index into local ++ fixed), the (keyframe slot, keypoint index)
+ *                     behind it, (u, v, ur) from kf_keypoint[idx] and kf_uright, inv_sigma2[octave], the keyframe's
+ *                     fx fy cx cy bf.  pose_fixed = (kf_id == 0) for a local keyframe, 1 for a fixed camera.
+ *    counts[0 .. 4)   n_local, n_fixed, n_points, n_edges; counts[4] the status: ORBBA_WINDOW_OK, or
+ *                     ORBBA_WINDOW_OVERFLOW when n_local + n_fixed > cap_poses, n_points > cap_points or n_edges >
+ *                     cap_edges: the four counts are then the sizes needed and no other array of the window is
+ *                     written; the other two parts do nothing on such a window.  counts[5]: every edge's camera is
+ *                     cur's, bit for bit.  counts has ORBBA_WINDOW_COUNTS entries.
+ *    Integer atomicMin "first position" words per slot, flags, one-workgroup scans and stable compactions: no
+ *    floating-point atomics, and the result does not depend on the order anything runs in: two runs are byte-identical.
+ *
+ * 2. LocalBA on the window, inside orbba_local_ba_map: a kernel fills orbba_local_ba's device problem from the window
+ *    (q from the float pose by the host's quat_from_R, everything else by exact float-to-double widening, mono by
+ *    ur < 0); pose_fixed, edge_point, edge_pose and the counts come back for the structure build, nothing else of the
+ *    window crosses PCIe.  The kernels and the LM control are orbba_local_ba's, and so are its environment knobs.
+ *
+ * 3. The write-back (:677-735), orbba_local_ba_apply; skipped entirely by orbba_local_ba_map when ran == 0.
+ *    For every edge flagged outlier, in edge order, EraseMapPointMatch then EraseObservation: if the point still
+ *    observes the keyframe, kf_mappoint[kf][idx] = -1, mp_nobs -= (kf_uright[kf][idx] >= 0 ? 2 : 1), the observation is
+ *    erased (mp_obs_kf = -1), mp_ref_kf == kf becomes the first remaining observation in CSR order or -1, and mp_nobs
+ *    <= 2 gives SetBadFlag (the culls' rules below); a point that has gone bad observes nothing, so its later outlier
+ *    edges do nothing.  Points run in parallel, a point's edges in order.  Then kf_pose of every local keyframe =
+ *    FromSE3Quat(estimate) (kf_id == 0 included), mp_xw of every local point = the narrowed estimate, and
+ *    UpdateNormalAndDepth over the local points (orbmm_update_normal_depth's).
+ * ---------------------------------------------------------------------------------------- */
+#define ORBBA_WINDOW_OK 0
+#define ORBBA_WINDOW_OVERFLOW 1
+#define ORBBA_WINDOW_COUNTS 8
+
+typedef struct orbba_window_map {
+    int32_t n_keyframes, n_mappoints, kf_cap, conn_cap, n_obs, n_levels;
+    const float*   inv_sigma2;      /* host memory, n_levels: pyramid.invSigmaSq */
+    const float*   scale_factors;   /* host memory, n_levels: pyramid.scaleFactors (UpdateNormalAndDepth) */
+    const int32_t* kf_id;           /* [K] */
+    const int32_t* kf_n;            /* [K] */
+    const uint8_t* kf_bad;          /* [K] */
+    int32_t*       kf_mappoint;     /* [K][kf_cap], updated */
+    const orbx_keypoint* kf_keypoint;   /* [K][kf_cap] keypointsUn, as orblm_batch holds them */
+    const int32_t* kf_kp_octave;    /* [K][kf_cap] keypointsUn[i].octave, the table orbmm_points takes; the window alone
+                                     * does not read it */
+    const float*   kf_uright;       /* [K][kf_cap] */
+    const float*   kf_camera;       /* [K][6] fx, fy, cx, cy, bf, baseline (orblm_batch's) */
+    float*         kf_pose;         /* [K][12] Rcw row-major, tcw; updated */
+    const int32_t* ord_slot;        /* [K][conn_cap] orderedConnectedKeyFrames_ */
+    const int32_t* n_ord;           /* [K] */
+    uint8_t*       mp_bad;          /* [M] updated */
+    float*         mp_xw;           /* [M][3] updated */
+    int32_t*       mp_nobs;         /* [M] updated */
+    int32_t*       mp_ref_kf;       /* [M] updated */
+    const int32_t* mp_obs_off;      /* [M + 1] */
+    int32_t*       mp_obs_kf;       /* updated: -1 where erased */
+    const int32_t* mp_obs_idx;
+    float*         mp_normal;       /* [M][3] updated */
+    float*         mp_max_min;      /* [M][2] updated */
+} orbba_window_map;
+
+typedef struct orbba_window {
+    int32_t  cap_poses, cap_points, cap_edges;
+    int32_t* counts;           /* ORBBA_WINDOW_COUNTS */
+    int32_t* pose_kf;          /* [cap_poses] keyframe slot of each vertex: local, then fixed */
+    uint8_t* pose_fixed;       /* [cap_poses] */
+    int32_t* point;            /* [cap_points] map-point slot of each point vertex */
+    int32_t* edge_point;       /* [cap_edges] */
+    int32_t* edge_pose;        /* [cap_edges] */
+    int32_t* edge_kf;          /* [cap_edges] keyframe slot */
+    int32_t* edge_idx;         /* [cap_edges] keypoint index */
+    float*   edge_obs;         /* [cap_edges][3] u, v, ur */
+    float*   edge_inv_sigma2;  /* [cap_edges] */
+    float*   edge_cam;         /* [cap_edges][5] fx, fy, cx, cy, bf */
+} orbba_window;
+
+typedef struct orbba_map_result {
+    int32_t iterations[2];   /* orbba_result's */
+    double  chi2[2];
+    int32_t ran;             /* 0: the stop flag was set on entry; no table was written */
+    int32_t counts[4];       /* n_local, n_fixed, n_points, n_edges */
+    int32_t status;          /* ORBBA_WINDOW_* */
+} orbba_map_result;
+
+/* Device forms: every array in HBM but inv_sigma2 and scale_factors; enqueue only on `stream`.  ORB_EINVAL for a NULL
+ * required array, negative sizes or capacities, kf_cap or conn_cap < 1, n_levels outside [1, 32] and a table (or
+ * (conn_cap + 1) * kf_cap) of 2^31 entries or more.  The workspace (per thread, grow-only: 20 bytes per keyframe, 24 per
+ * map point) belongs to the calling thread: its calls must be stream-ordered.
+ * orbba_local_window_device reads kf_id, kf_n, kf_bad, kf_mappoint, kf_keypoint, kf_uright, kf_camera, ord_slot, n_ord,
+ * mp_bad and the CSR; the others may be NULL there.  Nothing is copied back.
+ * orbba_local_ba_apply_device: outlier[n_edges], pose_R[n_poses][9], pose_t[n_poses][3], points[n_points][3] in HBM, in
+ * the window's order (orbba_result's arrays).
+ * orbba_local_ba_map_device: parts 1 to 3 on `stream`, ordered after what it holds at entry.  The LM loop is
+ * host-driven, so the call returns once the loop has ended; work enqueued on `stream` afterwards sees the applied
+ * tables (the write-back may still be in flight at return).  window: the caller's buffers for the window, kept as the
+ * call leaves them.  On ORBBA_WINDOW_OVERFLOW the call returns ORB_OK with result->status set, ran = 0 and no table
+ * written.  More than ORBBA_MAX_FREE_KEYFRAMES free keyframes: ORB_EINVAL.  stop_flag as in orbba_local_ba. */
+int orbba_local_window_device(const orbba_window_map* map, int32_t cur, const orbba_window* window, void* stream);
+int orbba_local_ba_apply_device(const orbba_window_map* map, const orbba_window* window, const uint8_t* outlier,
+                                const double* pose_R, const double* pose_t, const double* points, void* stream);
+int orbba_local_ba_map_device(const orbba_window_map* map, int32_t cur, const orbba_window* window,
+                              orbba_map_result* result, const volatile int32_t* stop_flag, void* stream);
+/* Host forms: every pointer is host memory, synchronous; the updated arrays are written back.  Before anything is
+ * copied, besides the checks above: cur in [0, n_keyframes), the offsets start at 0, do not decrease and end within
+ * n_obs, mp_obs_kf in [-1, n_keyframes), mp_obs_idx in [0, kf_cap) and the octave of that keypoint in [0, n_levels),
+ * kf_mappoint in [-1, n_mappoints), mp_ref_kf in [-1, n_keyframes), kf_n in [0, kf_cap], n_ord in [0, conn_cap] and the
+ * first n_ord entries of a row in [0, n_keyframes), no point twice in a keyframe's row, no keyframe twice in a point's
+ * observations; for the apply the window's counts within its capacities and its indices within the counts.
+ * ORB_EINVAL otherwise.  orbba_local_ba_map sizes the window itself (n_keyframes poses, n_mappoints points, n_obs
+ * edges). */
+int orbba_local_window(const orbba_window_map* map, int32_t cur, const orbba_window* window, int device);
+int orbba_local_ba_apply(const orbba_window_map* map, const orbba_window* window, const uint8_t* outlier,
+                         const double* pose_R, const double* pose_t, const double* points, int device);
+int orbba_local_ba_map(const orbba_window_map* map, int32_t cur, orbba_map_result* result,
+                       const volatile int32_t* stop_flag, int device);
+
+/* ------------------------------------------------------------------------------------------
  * void Optimizer::BundleAdjustment(keyframes, mappoints, nIterations, stopFlag, loopKFId, robust)
  * (include/Optimizer.h, src/Optimizer.cc:197-343), which Optimizer::GlobalBundleAdjustemnt (LoopClosing's GlobalBA
  * thread, LoopClosing.cc:366: 10 iterations, not robust) and Tracking::CreateInitialMapMonocular (Tracking.cc:1136:

@@ -301,6 +301,46 @@ inline bool LocalBundleAdjustment(const orbba_problem& problem, orbba_result& re
     return result.ran != 0;
 }
 
+// Optimizer::LocalBundleAdjustment(currKF, stopFlag, map) as a whole (Optimizer.cc:491-736), in place on the slot tables
+// in HBM (orbba_window_map): the window gather, LocalBA staged from it on the device and the write-back, enqueued on one
+// stream.  The *Host members take host arrays and are synchronous.
+class LocalBA {
+public:
+    explicit LocalBA(const orbba_window_map& map) : map_(map) {}
+
+    // :493-631: local keyframes, local points, fixed cameras and edges into window, in orbba_problem's order
+    void Window(int32_t cur, const orbba_window& window, void* stream = nullptr) const {
+        check(orbba_local_window_device(&map_, cur, &window, stream), "orbba_local_window_device");
+    }
+    // :677-735 on given flags and estimates (HBM, the window's order): erasures, poses, points, UpdateNormalAndDepth
+    void Apply(const orbba_window& window, const uint8_t* d_outlier, const double* d_pose_R, const double* d_pose_t,
+               const double* d_points, void* stream = nullptr) const {
+        check(orbba_local_ba_apply_device(&map_, &window, d_outlier, d_pose_R, d_pose_t, d_points, stream),
+              "orbba_local_ba_apply_device");
+    }
+    // The whole call.  Returns false when nothing was optimised or written: the stop flag was set on entry, or
+    // result.status == ORBBA_WINDOW_OVERFLOW (result.counts are then the sizes the window needs).
+    bool Run(int32_t cur, const orbba_window& window, orbba_map_result& result, const volatile int32_t* stopFlag = nullptr,
+             void* stream = nullptr) const {
+        check(orbba_local_ba_map_device(&map_, cur, &window, &result, stopFlag, stream), "orbba_local_ba_map_device");
+        return result.ran != 0;
+    }
+    void WindowHost(int32_t cur, const orbba_window& window, int device = 0) const {
+        check(orbba_local_window(&map_, cur, &window, device), "orbba_local_window");
+    }
+    void ApplyHost(const orbba_window& window, const uint8_t* outlier, const double* pose_R, const double* pose_t,
+                   const double* points, int device = 0) const {
+        check(orbba_local_ba_apply(&map_, &window, outlier, pose_R, pose_t, points, device), "orbba_local_ba_apply");
+    }
+    bool RunHost(int32_t cur, orbba_map_result& result, const volatile int32_t* stopFlag = nullptr, int device = 0) const {
+        check(orbba_local_ba_map(&map_, cur, &result, stopFlag, device), "orbba_local_ba_map");
+        return result.ran != 0;
+    }
+
+private:
+    orbba_window_map map_;
+};
+
 // void Optimizer::BundleAdjustment(keyframes, mappoints, nIterations, stopFlag, loopKFId, robust)
 // (Optimizer.cc:197-343) from the flattened graph (:212-294, pose_fixed = (id == 0)), with the reference's edge
 // typing (`if (ur)`).  The caller writes result.pose_f / points_f to TcwGBA / posGBA and sets BAGlobalForKF

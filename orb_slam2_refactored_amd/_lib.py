@@ -386,6 +386,27 @@ class OrbmmCull(C.Structure):
                                   "conn_weight", "n_conn", "ord_slot", "ord_weight", "n_ord", "kf_parent", "kf_covis")]
 
 
+class OrbbaWindowMap(C.Structure):
+    """orbba_window_map (include/orbslam2_amd.h)."""
+    _fields_ = [(k, C.c_int32) for k in ("n_keyframes", "n_mappoints", "kf_cap", "conn_cap", "n_obs", "n_levels")] + [
+        (k, C.c_void_p) for k in ("inv_sigma2", "scale_factors", "kf_id", "kf_n", "kf_bad", "kf_mappoint", "kf_keypoint",
+                                  "kf_kp_octave", "kf_uright", "kf_camera", "kf_pose", "ord_slot", "n_ord", "mp_bad", "mp_xw",
+                                  "mp_nobs", "mp_ref_kf", "mp_obs_off", "mp_obs_kf", "mp_obs_idx", "mp_normal", "mp_max_min")]
+
+
+class OrbbaWindow(C.Structure):
+    """orbba_window (include/orbslam2_amd.h)."""
+    _fields_ = [(k, C.c_int32) for k in ("cap_poses", "cap_points", "cap_edges")] + [
+        (k, C.c_void_p) for k in ("counts", "pose_kf", "pose_fixed", "point", "edge_point", "edge_pose", "edge_kf", "edge_idx",
+                                  "edge_obs", "edge_inv_sigma2", "edge_cam")]
+
+
+class OrbbaMapResult(C.Structure):
+    """orbba_map_result (include/orbslam2_amd.h)."""
+    _fields_ = [("iterations", C.c_int32 * 2), ("chi2", C.c_double * 2), ("ran", C.c_int32), ("counts", C.c_int32 * 4),
+                ("status", C.c_int32)]
+
+
 SIGNATURES = {    "orbx_create": (C.c_int, [C.POINTER(OrbxParams), C.c_int, C.POINTER(VP)]),
     "orbx_destroy": (C.c_int, [VP]),
     "orbx_scale_tables": (C.c_int, [VP, VP, VP, VP, VP, VP]),
@@ -486,6 +507,13 @@ SIGNATURES = {    "orbx_create": (C.c_int, [C.POINTER(OrbxParams), C.c_int, C.PO
     "orbdb_read_slots": (C.c_int, [VP, VP, VP]),
     "orbtl_track_local_map_device": (C.c_int, [C.POINTER(OrbtlMap), C.POINTER(OrbtlFrames), C.POINTER(OrbtlResult), VP]),
     "orbtl_track_local_map": (C.c_int, [C.POINTER(OrbtlMap), C.POINTER(OrbtlFrames), C.POINTER(OrbtlResult), C.c_int]),
+    "orbba_local_window_device": (C.c_int, [C.POINTER(OrbbaWindowMap), C.c_int32, C.POINTER(OrbbaWindow), VP]),
+    "orbba_local_window": (C.c_int, [C.POINTER(OrbbaWindowMap), C.c_int32, C.POINTER(OrbbaWindow), C.c_int]),
+    "orbba_local_ba_apply_device": (C.c_int, [C.POINTER(OrbbaWindowMap), C.POINTER(OrbbaWindow), VP, VP, VP, VP, VP]),
+    "orbba_local_ba_apply": (C.c_int, [C.POINTER(OrbbaWindowMap), C.POINTER(OrbbaWindow), VP, VP, VP, VP, C.c_int]),
+    "orbba_local_ba_map_device": (C.c_int, [C.POINTER(OrbbaWindowMap), C.c_int32, C.POINTER(OrbbaWindow),
+                                            C.POINTER(OrbbaMapResult), VP, VP]),
+    "orbba_local_ba_map": (C.c_int, [C.POINTER(OrbbaWindowMap), C.c_int32, C.POINTER(OrbbaMapResult), VP, C.c_int]),
     "orbmm_update_normal_depth_device": (C.c_int, [C.POINTER(OrbmmPoints), VP]),
     "orbmm_update_normal_depth": (C.c_int, [C.POINTER(OrbmmPoints), C.c_int]),
     "orbmm_update_connections_device": (C.c_int, [C.POINTER(OrbmmGraph), C.c_int32, VP, VP]),

@@ -37,6 +37,7 @@
 #include "common.h"
 #include "host_helper.h"
 #include "se3.h"
+#include "ba_window.h"
 
 #include "orbba_dev.h"
 #include "orbba_linearize.h"
@@ -77,6 +78,7 @@ struct BAContext {
     int device = -1;
     hipStream_t st = nullptr;
     DevBuf prob, state, structure, sys, ctlbuf;
+    DevBuf res_dev;   // the results of a call on a device-resident window (ResultLayout, then pose_R)
     BACtl* h_ctl = nullptr;   // pinned
     BACtl* h_ring = nullptr;  // pinned, device-mapped control snapshots, one per step in flight
     BACtl* d_ring = nullptr;
@@ -86,7 +88,7 @@ struct BAContext {
     PinnedBuf h_prob, h_struct, h_res;   // pinned staging images (one copy each way)
     int next_seq() const { return step_seq == 0x7fffffff ? 1 : step_seq + 1; }   // the id after step_seq
     void release() {   // everything device-bound
-        prob.release(); state.release(); structure.release(); sys.release(); ctlbuf.release();
+        prob.release(); state.release(); structure.release(); sys.release(); ctlbuf.release(); res_dev.release();
         if (st) { (void)hipStreamDestroy(st); st = nullptr; }
         if (h_ring) { (void)hipHostFree(h_ring); h_ring = nullptr; d_ring = nullptr; }
         if (h_stop) { (void)hipHostFree(h_stop); h_stop = nullptr; d_stop = nullptr; }
@@ -268,6 +270,44 @@ static int raise_solve_lds_limit(SolveKernel which, int device, size_t ldlt_lds)
     return ORB_OK;
 }
 
+// The second staging path: UploadLayout filled in HBM from a gathered window (ba_window.h), the values stage_problem
+// copies from the host.  q by the host's quat_from_R on the widened rotation, everything else an exact widening.
+__global__ __launch_bounds__(256) void ba_stage_window_kernel(BaWindowRun r, UploadLayout up, int one_cam) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    const int P = r.n_local + r.n_fixed;
+    if (i < P) {
+        const int k = r.w.pose_kf[i];
+        double R[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1}, t[3] = {0, 0, 0};
+        if (k >= 0 && k < r.K) {
+            for (int j = 0; j < 9; j++) R[j] = (double)r.kf_pose[12 * (size_t)k + j];
+            for (int j = 0; j < 3; j++) t[j] = (double)r.kf_pose[12 * (size_t)k + 9 + j];
+        }
+        quat_from_R(R, up.q + 4 * (size_t)i);
+        for (int j = 0; j < 3; j++) up.t[3 * (size_t)i + j] = t[j];
+        up.fixed[i] = r.w.pose_fixed[i];
+    }
+    if (i < r.n_points) {
+        const int p = r.w.point[i];
+        for (int j = 0; j < 3; j++) up.X[3 * (size_t)i + j] = (p >= 0 && p < r.M) ? (double)r.mp_xw[3 * (size_t)p + j] : 0.0;
+    }
+    if (i < r.n_edges) {
+        up.ep[i] = r.w.edge_point[i];
+        up.ek[i] = r.w.edge_pose[i];
+        const float ur = r.w.edge_obs[3 * (size_t)i + 2];
+        up.stereo[i] = ur < 0 ? 0 : 1;   // ur < 0 => mono (:595)
+        for (int j = 0; j < 3; j++) up.obs[3 * (size_t)i + j] = (double)r.w.edge_obs[3 * (size_t)i + j];
+        up.info[i] = (double)r.w.edge_inv_sigma2[i];
+        if (!one_cam || i == 0)
+            for (int j = 0; j < 5; j++) up.cam[5 * (size_t)i + j] = (double)r.w.edge_cam[5 * (size_t)i + j];
+    }
+}
+
+// toRotationMatrix of the gathered estimates, as finish() does on the host
+__global__ __launch_bounds__(256) void ba_result_rotation_kernel(const double* q, double* R, int P) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i < P) q_to_R(q + 4 * (size_t)i, R + 9 * (size_t)i);
+}
+
 // One orbba_local_ba call.
 struct LocalBACall {
     const orbba_problem* pr;
@@ -284,6 +324,9 @@ struct LocalBACall {
     FillQueue fills;   // flushed (one launch) before the first kernel that reads them
     ResultLayout dres{};   // the kernels' view of the mapped pinned result region
     int n_gather = 0;
+    BaWindowRun* win = nullptr;   // the problem is a gathered window in HBM: the second staging path
+    hipStream_t win_stream = nullptr;
+    orbba_problem* win_pr = nullptr;   // pr, writable: its three host arrays are set by stage_window
     uint8_t* d_level = nullptr;   // b.level, writable (the classification between the loops sets it)
     // the host half of the structure build, posted to the helper thread
     bool counts_ok = false;
@@ -326,7 +369,7 @@ struct LocalBACall {
 
     int validate() {
         ORB_CHECK_ARG(P >= 0 && N >= 0 && E >= 0, "negative sizes");
-        ORB_CHECK_ARG(res->pose_R && res->pose_t && res->points && (res->edge_outlier || !sch.classify),
+        ORB_CHECK_ARG(win || (res->pose_R && res->pose_t && res->points && (res->edge_outlier || !sch.classify)),
                       "null result buffers");
         tm.mark("entry");
         for (int e = 0; e < E; e++)
@@ -389,6 +432,44 @@ struct LocalBACall {
         std::memcpy(h.q, q0.data(), 32 * (size_t)P);
         std::memcpy(h.t, pr->pose_t, 24 * (size_t)P);
         std::memcpy(h.X, pr->points, 24 * (size_t)N);
+        ORB_HIP_TRY(hipMemcpyAsync(C.prob.ptr, C.h_prob.ptr, up_bytes, hipMemcpyHostToDevice, st));
+        dres.carve(C.h_res.dptr, P, N, E);
+        return bind_problem(up, s, one_cam);
+    }
+
+    // The window's form of stage_problem: the same region filled by a kernel; pose_fixed, edge_point and edge_pose (the
+    // region's first three fields) come back for the structure build, the results stay in HBM.
+    int stage_window() {
+        const bool one_cam = E > 0 && win->one_cam;
+        UploadLayout up, h;
+        StateLayout s;
+        const size_t up_bytes = up.carve(nullptr, P, N, E, one_cam);
+        const size_t res_bytes = dres.carve(nullptr, P, N, E);
+        int rc;
+        if ((rc = C.prob.reserve(up_bytes))) return rc;
+        if ((rc = C.state.reserve(s.carve(nullptr, P, N, E)))) return rc;
+        if ((rc = C.ctlbuf.reserve(sizeof(BACtl) + 64))) return rc;
+        if ((rc = C.h_prob.ensure(up_bytes))) return rc;
+        if ((rc = C.res_dev.reserve(res_bytes + 72 * (size_t)P + 256))) return rc;
+        up.carve(C.prob.as<char>(), P, N, E, one_cam);
+        h.carve(C.h_prob.ptr, P, N, E, one_cam);
+        s.carve(C.state.as<char>(), P, N, E);
+        dres.carve(C.res_dev.as<char>(), P, N, E);
+        const int n = std::max(E, std::max(N, P));
+        if (n) hipLaunchKernelGGL(ba_stage_window_kernel, dim3((n + 255) / 256), dim3(256), 0, st, *win, up, one_cam ? 1 : 0);
+        ORB_HIP_TRY(hipGetLastError());
+        const size_t back = (size_t)((char*)up.stereo - (char*)up.fixed);   // fixed, ep, ek
+        ORB_HIP_TRY(hipMemcpyAsync(C.h_prob.ptr, C.prob.ptr, back, hipMemcpyDeviceToHost, st));
+        ORB_HIP_TRY(hipStreamSynchronize(st));
+        win_pr->pose_fixed = h.fixed;
+        win_pr->edge_point = h.ep;
+        win_pr->edge_pose = h.ek;
+        if ((rc = validate())) return rc;
+        return bind_problem(up, s, one_cam);
+    }
+
+    int bind_problem(const UploadLayout& up, const StateLayout& s, bool one_cam) {
+        int rc;
         b.P = P; b.N = N; b.E = E;
         b.q = up.q; b.t = up.t; b.X = up.X;
         b.q_sv = s.q_sv; b.t_sv = s.t_sv; b.X_sv = s.X_sv;
@@ -401,15 +482,13 @@ struct LocalBACall {
         b.stop_after = opt.stop_after;
         // (the control block is written whole by the first optimize()'s fill: trials / stopped count from 0
         // over the whole call)
-        ORB_HIP_TRY(hipMemcpyAsync(C.prob.ptr, C.h_prob.ptr, up_bytes, hipMemcpyHostToDevice, st));
         if ((rc = fills.add(s.robust, E, sch.robust ? 1 : 0, st)) || (rc = fills.add(s.level, E, 0, st)) ||
             (rc = fills.add(s.err, 24 * (size_t)E, 0, st)))
             return rc;
         res->iterations[0] = res->iterations[1] = 0;
         res->chi2[0] = res->chi2[1] = 0;
         // the final classification + poses / points are gathered straight into the mapped pinned result
-        // region (round 6: no device-to-host copy behind the kernel)
-        dres.carve(C.h_res.dptr, P, N, E);
+        // region (round 6: no device-to-host copy behind the kernel); a window's stay in HBM
         n_gather = std::max(E, std::max(N, P));
         tm.mark("staging + upload enqueued");
         return ORB_OK;
@@ -703,6 +782,7 @@ struct LocalBACall {
             gather(0);
             ORB_HIP_TRY(hipGetLastError());
         }
+        if (win) return finish_window(ran);
         ORB_HIP_TRY(hipStreamSynchronize(st));
         tm.mark("results copied");
         ResultLayout h;
@@ -737,14 +817,34 @@ struct LocalBACall {
         return ORB_OK;
     }
 
+    // a window's results: the gather's region and the rotations behind it, for the write-back enqueued next
+    int finish_window(bool ran) {
+        ResultLayout size;
+        double* R = reinterpret_cast<double*>(C.res_dev.as<char>() + align_up(size.carve(nullptr, P, N, E), 256));
+        if (ran && P) hipLaunchKernelGGL(ba_result_rotation_kernel, dim3((P + 255) / 256), dim3(256), 0, st, dres.q, R, P);
+        ORB_HIP_TRY(hipGetLastError());
+        win->outlier = dres.outlier;
+        win->pose_R = R;
+        win->pose_t = dres.t;
+        win->points = dres.X;
+        if (helper_wait.on) {
+            C.helper.wait();
+            helper_wait.on = false;
+        }
+        tm.mark("end");
+        if (tm.on) tm.report();
+        return ORB_OK;
+    }
+
     int run() {
         int rc;
-        if ((rc = validate()) || (rc = C.acquire(device))) return rc;
-        st = C.st;
+        if (!win && (rc = validate())) return rc;
+        if ((rc = C.acquire(device))) return rc;
+        st = win ? win_stream : C.st;
         *C.h_stop = stopped() ? 1 : 0;
         tm.mark("context");
-        post_counts();
-        if ((rc = stage_problem())) return rc;
+        if (!win) post_counts();
+        if ((rc = win ? stage_window() : stage_problem())) return rc;
         const bool ran = !stopped() && opt.stop_after != 0;   // Optimizer.cc:633-634: stop before optimising => nothing done
         res->ran = ran ? 1 : 0;
         if (ran) {
@@ -770,6 +870,29 @@ thread_local HostStructure g_hs;   // capacity kept across calls
 
 
 }  // namespace
+
+// orbba_local_ba on a window gathered in HBM (orbbamap.hip calls it between its gather and its write-back): the call
+// runs on `stream`, on the calling thread's current device.
+int orbamd::orbba_run_window(BaWindowRun& r, const volatile int32_t* stop_flag, void* stream) {
+    int dev = 0;
+    ORB_HIP_TRY(hipGetDevice(&dev));
+    orbba_problem pr{};
+    pr.n_poses = r.n_local + r.n_fixed;
+    pr.n_points = r.n_points;
+    pr.n_edges = r.n_edges;
+    BAOutputs o{};
+    LocalBACall call(&pr, &o, LOCAL_BA_SCHEDULE, stop_flag, dev, g_ba, g_hs);
+    call.win = &r;
+    call.win_stream = (hipStream_t)stream;
+    call.win_pr = &pr;
+    const int rc = call.run();
+    for (int k = 0; k < 2; k++) {
+        r.iterations[k] = o.iterations[k];
+        r.chi2[k] = o.chi2[k];
+    }
+    r.ran = o.ran;
+    return rc;
+}
 
 extern "C" int orbba_local_ba(const orbba_problem* pr, orbba_result* res, const volatile int32_t* stop_flag,
                               int device) {

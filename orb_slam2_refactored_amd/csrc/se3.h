@@ -66,7 +66,7 @@ __device__ __forceinline__ void q_normalize_pos(Q4& q) {   // SE3Quat::normalize
 }
 // The host's initial estimates, SE3Quat(R, t) -> Quaterniond(R) normalised (Optimizer.cc:145-150), with
 // Eigen's four divisions.
-inline void quat_from_R(const double* m, double* q4) {
+__host__ __device__ __forceinline__ void quat_from_R(const double* m, double* q4) {
     Q4 q = q_from_R(m);
     if (q.w < 0) { q.x = -q.x; q.y = -q.y; q.z = -q.z; q.w = -q.w; }
     const double n = sqrt(q.x * q.x + q.y * q.y + q.z * q.z + q.w * q.w);

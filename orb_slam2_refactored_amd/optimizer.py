@@ -10,8 +10,8 @@ import ctypes as C
 
 import numpy as np
 
-from ._lib import (BAProblem, BAResult, EssentialGraph, EssentialGraphResult, EssentialGraphTables, GBAMap, GBAOptions,
-                   GBAResult, OptSim3Batch, OptSim3Result, PoseBatch, PoseResult, check, lib, ptr, stream_ptr, tptr)
+from ._lib import (KP_DTYPE, BAProblem, BAResult, EssentialGraph, EssentialGraphResult, EssentialGraphTables, GBAMap,
+                   GBAOptions, GBAResult, OrbbaMapResult, OrbbaWindow, OrbbaWindowMap, OptSim3Batch, OptSim3Result, PoseBatch, PoseResult, check, lib, ptr, stream_ptr, tptr)
 
 
 def _need(arrays: dict, counts: dict, what: str):
@@ -427,3 +427,201 @@ def essential_graph_edges(tables: dict, min_weight: int = 100):
     check(lib().orbba_essential_graph_edges(C.byref(t), int(min_weight), E, ptr(ei), ptr(ej), ptr(et), ptr(n)),
           "orbba_essential_graph_edges")
     return ei[:E], ej[:E], et[:E]
+
+
+# ---- LocalBundleAdjustment on the device-resident map (orbba_local_window / _apply / _map, include/orbslam2_amd.h)
+WINDOW_OK, WINDOW_OVERFLOW = 0, 1
+# orbba_window_map's arrays in struct order: name -> (dtype, shape); K keyframes, M map points, M1 = M + 1, L levels.
+# kf_keypoint: KP_DTYPE records on the host, their bytes as (K, kf_cap, 7) float32 on the device.
+WINDOW_MAP_KEYS = {
+    "inv_sigma2": (np.float32, ("L",)), "scale_factors": (np.float32, ("L",)), "kf_id": (np.int32, ("K",)),
+    "kf_n": (np.int32, ("K",)), "kf_bad": (np.uint8, ("K",)), "kf_mappoint": (np.int32, ("K", "kf_cap")),
+    "kf_keypoint": (KP_DTYPE, ("K", "kf_cap")), "kf_kp_octave": (np.int32, ("K", "kf_cap")),
+    "kf_uright": (np.float32, ("K", "kf_cap")), "kf_camera": (np.float32, ("K", 6)), "kf_pose": (np.float32, ("K", 12)),
+    "ord_slot": (np.int32, ("K", "conn_cap")), "n_ord": (np.int32, ("K",)), "mp_bad": (np.uint8, ("M",)),
+    "mp_xw": (np.float32, ("M", 3)), "mp_nobs": (np.int32, ("M",)), "mp_ref_kf": (np.int32, ("M",)),
+    "mp_obs_off": (np.int32, ("M1",)), "mp_obs_kf": (np.int32, ("n_obs",)), "mp_obs_idx": (np.int32, ("n_obs",)),
+    "mp_normal": (np.float32, ("M", 3)), "mp_max_min": (np.float32, ("M", 2)),
+}
+WINDOW_HOST_KEYS = ("inv_sigma2", "scale_factors")   # host memory in both forms
+WINDOW_GATHER_KEYS = ("inv_sigma2", "kf_id", "kf_n", "kf_bad", "kf_mappoint", "kf_keypoint", "kf_uright", "kf_camera", "ord_slot",
+                      "n_ord", "mp_bad", "mp_obs_off", "mp_obs_kf", "mp_obs_idx")
+WINDOW_UPDATED = ("kf_mappoint", "kf_pose", "mp_bad", "mp_xw", "mp_nobs", "mp_ref_kf", "mp_obs_kf", "mp_normal", "mp_max_min")
+# orbba_window's arrays in struct order: name -> (dtype, capacity, row width)
+WINDOW_KEYS = {"counts": (np.int32, None, 8), "pose_kf": (np.int32, "poses", 1), "pose_fixed": (np.uint8, "poses", 1),
+               "point": (np.int32, "points", 1), "edge_point": (np.int32, "edges", 1), "edge_pose": (np.int32, "edges", 1),
+               "edge_kf": (np.int32, "edges", 1), "edge_idx": (np.int32, "edges", 1), "edge_obs": (np.float32, "edges", 3),
+               "edge_inv_sigma2": (np.float32, "edges", 1), "edge_cam": (np.float32, "edges", 5)}
+
+
+def _window_dims(t: dict):
+    for k in ("kf_mappoint", "ord_slot", "mp_bad", "mp_obs_kf", "inv_sigma2"):
+        if t.get(k) is None:
+            raise ValueError(f"{k} is required")
+    if len(t["kf_mappoint"].shape) != 2 or len(t["ord_slot"].shape) != 2:
+        raise ValueError("kf_mappoint and ord_slot must have two dimensions")
+    M = int(t["mp_bad"].shape[0])
+    return {"K": int(t["kf_mappoint"].shape[0]), "M": M, "M1": M + 1, "kf_cap": int(t["kf_mappoint"].shape[1]),
+            "conn_cap": int(t["ord_slot"].shape[1]), "n_obs": int(t["mp_obs_kf"].shape[0]), "L": len(t["inv_sigma2"])}
+
+
+def _window_map(tables: dict, keys, on_device: bool, keep: list, updated=()):
+    """(orbba_window_map, the arrays by name) over `keys` of the tables; the others stay NULL."""
+    d = _window_dims(tables)
+    arrays, addr = {}, {}
+    for k in keys:
+        dt, spec = WINDOW_MAP_KEYS[k]
+        want = tuple(d[x] if isinstance(x, str) else x for x in spec)
+        a = tables.get(k)
+        if a is None:
+            raise ValueError(f"{k} is required")
+        if on_device and k not in WINDOW_HOST_KEYS:
+            import torch
+            tt, want = ((torch.float32, want + (7,)) if k == "kf_keypoint" else
+                        ({np.int32: torch.int32, np.uint8: torch.uint8, np.float32: torch.float32}[dt], want))
+            if not isinstance(a, torch.Tensor) or not a.is_cuda or a.dtype != tt or not a.is_contiguous() or tuple(a.shape) != want:
+                raise ValueError(f"{k} must be a contiguous {tt} GPU tensor of shape {want}")
+            addr[k] = a.data_ptr()
+            if not a.numel():
+                spare = torch.zeros(8, dtype=torch.int32, device=a.device)
+                keep.append(spare)
+                addr[k] = spare.data_ptr()
+        else:
+            a = np.ascontiguousarray(a)
+            if a.dtype != dt or a.shape != want:
+                raise ValueError(f"{k} must be {np.dtype(dt)} of shape {want}, not {a.dtype} {a.shape}")
+            if k in updated:
+                a = a.copy()
+            keep.append(a)
+            addr[k] = a.ctypes.data if a.size else ptr(np.zeros(8, np.int32)).value
+        arrays[k] = a
+    m = OrbbaWindowMap(d["K"], d["M"], d["kf_cap"], d["conn_cap"], d["n_obs"], d["L"], *[addr.get(k) for k in WINDOW_MAP_KEYS])
+    return m, arrays, d
+
+
+def _window_caps(d: dict, caps):
+    caps = caps or {}
+    return {"poses": int(caps.get("poses", d["K"])), "points": int(caps.get("points", d["M"])), "edges": int(caps.get("edges", d["n_obs"]))}
+
+
+def _window_struct(window: dict, caps: dict, on_device: bool, keep: list):
+    addr = {}
+    for k, (dt, cap, width) in WINDOW_KEYS.items():
+        n = (caps[cap] if cap else 1) * width
+        a = window[k]
+        if on_device:
+            if int(a.numel()) < n or not a.is_cuda or not a.is_contiguous():
+                raise ValueError(f"window {k} must be a contiguous GPU tensor of at least {n} entries")
+            addr[k] = a.data_ptr()
+        else:
+            if a.size < n or a.dtype != dt or not a.flags.c_contiguous:
+                raise ValueError(f"window {k} must be contiguous {np.dtype(dt)} of at least {n} entries")
+            addr[k] = a.ctypes.data
+        keep.append(a)
+    return OrbbaWindow(caps["poses"], caps["points"], caps["edges"], *[addr[k] for k in WINDOW_KEYS])
+
+
+def new_window(caps: dict, device=None) -> dict:
+    """Buffers of an orbba_window with the capacities caps = {"poses", "points", "edges"}: numpy arrays, or GPU tensors on
+    the torch device `device`.  A capacity of 0 still gets an address."""
+    shape = lambda cap, width: (max(caps[cap], 1) if cap else 1) * width   # noqa: E731
+    if device is None:
+        return {k: np.zeros(shape(cap, w), dt) for k, (dt, cap, w) in WINDOW_KEYS.items()}
+    import torch
+    tt = {np.int32: torch.int32, np.uint8: torch.uint8, np.float32: torch.float32}
+    return {k: torch.zeros(shape(cap, w), dtype=tt[dt], device=device) for k, (dt, cap, w) in WINDOW_KEYS.items()}
+
+
+def LocalWindow(tables: dict, cur: int, caps: dict | None = None, window: dict | None = None, device: int = 0) -> dict:
+    """The window of LocalBundleAdjustment(cur) (src/Optimizer.cc:493-631) on `tables` (WINDOW_GATHER_KEYS of
+    WINDOW_MAP_KEYS, numpy): the arrays of WINDOW_KEYS at the capacities `caps` (default: K poses, M points, n_obs
+    edges), counts = n_local, n_fixed, n_points, n_edges, status (WINDOW_*), one camera.  `window` to write into given
+    buffers."""
+    keep = []
+    m, _, d = _window_map(tables, WINDOW_GATHER_KEYS, False, keep)
+    caps = _window_caps(d, caps)
+    window = window if window is not None else new_window(caps)
+    w = _window_struct(window, caps, False, keep)
+    check(lib().orbba_local_window(C.byref(m), int(cur), C.byref(w), device), "orbba_local_window")
+    return window
+
+
+def local_window_device(tables: dict, cur: int, caps: dict | None = None, window: dict | None = None, stream=None) -> dict:
+    """Device form: GPU tensors but for inv_sigma2; the window's tensors (`window` to reuse them).  Enqueue only on
+    `stream`."""
+    keep = []
+    m, a, d = _window_map(tables, WINDOW_GATHER_KEYS, True, keep)
+    caps = _window_caps(d, caps)
+    window = window if window is not None else new_window(caps, a["mp_bad"].device)
+    w = _window_struct(window, caps, True, keep)
+    check(lib().orbba_local_window_device(C.byref(m), int(cur), C.byref(w), stream_ptr(stream)), "orbba_local_window_device")
+    return window
+
+
+def _window_given_caps(window: dict):
+    n = lambda a: int(a.numel()) if hasattr(a, "numel") else int(a.size)   # noqa: E731
+    return {"poses": min(n(window["pose_kf"]), n(window["pose_fixed"])), "points": n(window["point"]),
+            "edges": min(n(window["edge_point"]), n(window["edge_obs"]) // 3, n(window["edge_cam"]) // 5)}
+
+
+def LocalBAApply(tables: dict, window: dict, outlier, pose_R, pose_t, points, device: int = 0) -> dict:
+    """LocalBundleAdjustment's write-back (:677-735) on `tables` (WINDOW_MAP_KEYS, numpy) for the edges flagged in
+    `outlier` and the estimates pose_R (P, 9), pose_t (P, 3), points (N, 3) in the window's order.  Returns the updated
+    copies of WINDOW_UPDATED."""
+    keep = []
+    m, a, d = _window_map(tables, tuple(k for k in WINDOW_MAP_KEYS), False, keep, WINDOW_UPDATED)
+    caps = _window_given_caps(window)
+    w = _window_struct(window, caps, False, keep)
+    fit = lambda x, dt, n: np.concatenate([np.ascontiguousarray(x, dt).reshape(-1), np.zeros(n, dt)])[:max(n, 1)].copy()   # noqa: E731
+    o, R, t, X = (fit(outlier, np.uint8, caps["edges"]), fit(pose_R, np.float64, 9 * caps["poses"]),
+                  fit(pose_t, np.float64, 3 * caps["poses"]), fit(points, np.float64, 3 * caps["points"]))
+    check(lib().orbba_local_ba_apply(C.byref(m), C.byref(w), ptr(o), ptr(R), ptr(t), ptr(X), device), "orbba_local_ba_apply")
+    return {k: a[k] for k in WINDOW_UPDATED}
+
+
+def local_ba_apply_device(tables: dict, window: dict, outlier, pose_R, pose_t, points, stream=None) -> None:
+    """Device form: WINDOW_UPDATED updated in place; outlier (uint8), pose_R, pose_t, points (float64) GPU tensors of at
+    least the window's capacities.  Enqueue only on `stream`."""
+    keep = []
+    m, _, d = _window_map(tables, tuple(k for k in WINDOW_MAP_KEYS), True, keep)
+    caps = _window_given_caps(window)
+    w = _window_struct(window, caps, True, keep)
+    for name, x, n in (("outlier", outlier, caps["edges"]), ("pose_R", pose_R, 9 * caps["poses"]),
+                       ("pose_t", pose_t, 3 * caps["poses"]), ("points", points, 3 * caps["points"])):
+        if not x.is_cuda or not x.is_contiguous() or int(x.numel()) < n:
+            raise ValueError(f"{name} must be a contiguous GPU tensor of at least {n} entries")
+    check(lib().orbba_local_ba_apply_device(C.byref(m), C.byref(w), outlier.data_ptr(), pose_R.data_ptr(), pose_t.data_ptr(),
+                                            points.data_ptr(), stream_ptr(stream)), "orbba_local_ba_apply_device")
+
+
+def _map_result(r: OrbbaMapResult) -> dict:
+    return dict(iterations=tuple(r.iterations), chi2=tuple(r.chi2), ran=bool(r.ran), counts=tuple(r.counts), status=int(r.status))
+
+
+def LocalBundleAdjustmentMap(tables: dict, cur: int, stop_flag=None, device: int = 0):
+    """Optimizer::LocalBundleAdjustment(cur, stopFlag, map) as a whole (src/Optimizer.cc:491-736) on `tables`
+    (WINDOW_MAP_KEYS, numpy).  Returns (the updated copies of WINDOW_UPDATED, dict(iterations, chi2, ran, counts,
+    status))."""
+    keep = []
+    m, a, _ = _window_map(tables, tuple(k for k in WINDOW_MAP_KEYS), False, keep, WINDOW_UPDATED)
+    r = OrbbaMapResult()
+    sf = _stop_flag_ptr(stop_flag, keep)
+    check(lib().orbba_local_ba_map(C.byref(m), int(cur), C.byref(r), sf, device), "orbba_local_ba_map")
+    return {k: a[k] for k in WINDOW_UPDATED}, _map_result(r)
+
+
+def local_ba_map_device(tables: dict, cur: int, window: dict | None = None, caps: dict | None = None, stop_flag=None,
+                        stream=None):
+    """Device form: the tables are GPU tensors updated in place, nothing of the map crosses to the host.  The LM loop is
+    host-driven, so the call returns once it has ended; work enqueued on `stream` afterwards sees the applied tables.
+    Returns (result dict, window)."""
+    keep = []
+    m, a, d = _window_map(tables, tuple(k for k in WINDOW_MAP_KEYS), True, keep)
+    caps = _window_caps(d, caps) if window is None else _window_given_caps(window)
+    window = window if window is not None else new_window(caps, a["mp_bad"].device)
+    w = _window_struct(window, caps, True, keep)
+    r = OrbbaMapResult()
+    sf = _stop_flag_ptr(stop_flag, keep)
+    check(lib().orbba_local_ba_map_device(C.byref(m), int(cur), C.byref(w), C.byref(r), sf, stream_ptr(stream)),
+          "orbba_local_ba_map_device")
+    return _map_result(r), window
