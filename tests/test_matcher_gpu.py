@@ -52,6 +52,29 @@ def test_bf_match_both_matrix_paths(oracle, monkeypatch, fp4, nA, nB):
         assert np.array_equal(g, e)
 
 
+@pytest.mark.parametrize("fp4", ["0", "1"])
+@pytest.mark.parametrize("nB", [31, 32, 33, 64, 65])
+@pytest.mark.parametrize("nA", [47, 48, 49, 127, 128, 129, 191, 192, 193])
+def test_bf_match_tile_edges(oracle, monkeypatch, fp4, nA, nB):
+    """Both matrix paths at their tile edges: nA around the wavefront and workgroup row counts (48 / 192
+    for FP4, 32 / 128 for i8), nB around a tile pair and the double buffer's parity.  The last column ties
+    with column 0 (a query one bit off it: best and second equal, the lower index wins; the last query
+    equals it), and an all-ones row sits on both sides."""
+    monkeypatch.setenv("ORBM_FP4", fp4)
+    rng = np.random.default_rng(1000 * nA + nB)
+    A = rand_desc(rng, nA)
+    B = rand_desc(rng, nB)
+    B[nB - 1] = B[0]
+    A[1] = B[0] ^ np.uint8(1)
+    A[nA - 1] = B[nB - 1]
+    A[0] = 0xFF
+    B[nB // 2] = 0xFF
+    got = ORBmatcher(0.6, False).MatchBruteForce(A, B)
+    exp = oracle.bf_match(A, B)
+    for g, e in zip(got, exp):
+        assert np.array_equal(g, e)
+
+
 @pytest.mark.parametrize("nA,nB", [(300, 2048), (300, 2049), (100, 4500)])
 def test_bf_match_chunked(oracle, nA, nB):
     """More than 2048 columns: the chunked kernel carries the top-2 across 2048-column chunks.

@@ -114,6 +114,35 @@ def test_c3_masks_and_only_stereo(oracle, tri_path):
             assert NM[p] == n and n > 0
 
 
+def test_c3_query_block_edges(oracle, tri_path):
+    """255 / 256 / 257 queries (one query block of the all-pairs kernels, exactly and one over) against
+    300 / 289 / 257 candidates: the keyframes' counts cut down to the first keypoints of extracted frames."""
+    import torch
+    P = 3
+    ex, frames, kps, desc, cnt = _c3_batch(P, 9300)
+    N = cnt.cpu().numpy().copy()
+    assert N.min() >= 300
+    N[:P] = [255, 256, 257]
+    N[P:] = [300, 289, 257]
+    ct = torch.from_numpy(N).cuda()
+    F12, _ = stereo_tri_geometry()
+    ep2 = np.array([650.0, 190.0], np.float32)
+    Ft = torch.from_numpy(np.tile(F12, (P, 1))).cuda()
+    Et = torch.from_numpy(np.tile(ep2, (P, 1))).cuda()
+    f1 = torch.arange(P, dtype=torch.int32, device="cuda")
+    scale, sigma2 = ex.GetScaleFactors(), ex.GetScaleSigmaSquares()
+    m12, nm = search_for_triangulation_batch_device(kps, desc, ct, kps, desc, ct, Ft, Et, scale, sigma2,
+                                                    frame1=f1, frame2=f1 + P)
+    torch.cuda.synchronize()
+    K, D = kps.cpu().numpy(), desc.cpu().numpy()
+    M, NM = m12.cpu().numpy(), nm.cpu().numpy()
+    for p in range(P):
+        q = P + p
+        exp, n = _oracle_pair(oracle, K[p], D[p], N[p], K[q], D[q], N[q], F12, ep2, scale, sigma2)
+        assert np.array_equal(M[p, :N[p]], exp), p
+        assert NM[p] == n
+
+
 def test_c3_event_overflow(oracle, tri_path):
     """Repeated descriptors: kf2 holds copies of four kf1 descriptors (and near copies), so those rows
     see a candidate with d <= TH_LOW at every column and the matrix path's per-lane event lists
