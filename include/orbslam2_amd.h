@@ -2263,6 +2263,173 @@ int orbba_essential_graph_edges_device(const orbba_eg_tables* g, int32_t n_loop_
                                        int32_t n_conn_slots, int32_t min_weight, int32_t capacity, int32_t* edge_i,
                                        int32_t* edge_j, uint8_t* edge_table, int32_t* n_edges, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Tracking's per-frame state (src/Tracking.cc): frame.mappoints, frame.outlier and the pose kept in HBM between the
+ * searches, orbtl_track_local_map_device and orbba_pose_optimization_device, batched over frames.  Seven small
+ * entries; none searches or optimises.  Per-element arithmetic: csrc/tf_frame.h.
+ *
+ * Frame tables, stride kp_cap per frame (the layout of orbtl_frames and the projection batches); an entry reads only
+ * the arrays its description names, the others may be NULL.  Map tables are those of orbtl_map / orbmm_observe.
+ * A slot read from device memory is not trusted: a map point outside [0, n_mappoints), a match outside its row, a
+ * keyframe outside [0, n_keyframes) counts as null; frame_n is clamped to [0, kp_cap]; orbtf_pose_edges, the
+ * one entry that indexes a table by an octave, clamps it into the table (orbtf_motion_project passes kp_octave through as
+ * mp_octave unchanged: the search behind it rejects an octave outside its own table).  Rows from frame_n[f] up are
+ * padding and are left as they are unless said otherwise.
+ * Frames of a batch are independent except that their mp_found increments add up (integer atomics): a batch equals
+ * its frames run one at a time.  No floating-point atomics: two runs are byte-identical.
+ *
+ * 1 orbtf_apply_matches: frame_mappoint[f][i] = src[row][kp_match[f][i]] for i < frame_n[f], where src is a table of
+ *   n_rows rows of src_cap slots and row = src_row[f] (NULL: row f): orbtl_result.local_mp (rows = frames), the last
+ *   frames' frame_mappoint, or kf_mappoint through the reference keyframe's slot.  ORBTF_MERGE writes only where
+ *   kp_match >= 0 (src/ORBmatcher.cc:376, the local-map search); ORBTF_REPLACE writes -1 where there is no match
+ *   (the std::fill + search of src/Tracking.cc:232-239, currFrame.mappoints = mappoints of :273).  The value written
+ *   is the source slot, -1 when that is outside [0, n_mappoints).
+ * 2 orbtf_pose_edges: the gather of src/Optimizer.cc:355-411.  Per frame the keypoints i < frame_n[f] with a map
+ *   point, in keypoint order, become the edges [edge_begin[f], edge_begin[f + 1]) of an orbba_pose_batch:
+ *   frame_outlier[f][i] = 0 for exactly those, xw = mp_xw widened, obs = (kp_xy, kp_uright), inv_sigma2 =
+ *   inv_sigma2_table[kp_octave] (float, n_levels entries, pyramid.invSigmaSq), edge_kp = i; pose_R / pose_t / cam are
+ *   pose / camera widened.  The edge arrays hold n_frames * kp_cap rows.  Mono / stereo typing stays with the
+ *   optimiser (ur < 0).  Two launches: count, then offsets and a stable compaction.
+ * 3 orbtf_finish_pose: frame_outlier[f][edge_kp[e]] = outlier[e] and pose = the double pose narrowed with one
+ *   rounding per element (FromSE3Quat, src/Optimizer.cc:157-162) for a frame with 3 edges or more (:413-415: a
+ *   frame with fewer keeps its pose and its zero flags).  Then over the keypoints with a map point, in order:
+ *   ORBTF_DISCARD (DiscardOutliers, src/Tracking.cc:187-211): an outlier's map point becomes -1 and its flag 0, and
+ *     its slot is appended to discarded[f][..] (n_discarded[f]; keypoint order; the points whose lastFrameSeen the
+ *     reference sets); n_inliers[f] counts the others that have mp_nobs > 0.
+ *   ORBTF_LOCAL_MAP (:664-680): a non-outlier gets mp_found += 1 and counts into n_inliers[f] when localization or
+ *     mp_nobs > 0; an outlier's map point becomes -1 only when stereo.
+ * 4 orbtf_motion_project (TrackWithMotionModel's setup): on the last frames' rows frame_mappoint[i] = mp_replaced[p]
+ *   where that is in [0, n_mappoints) (one step, :808-814); cur.pose[f] = velocity[f] * last.pose[f] in CameraPose's
+ *   float arithmetic (:225); motion[f] from tlc (src/ORBmatcher.cc:1286-1288; baseline[f] = camera.baseline); per last
+ *   keypoint the tests of :1295-1311 give mp_valid, mp_proj, mp_octave, mp_desc, mp_has_obs, mp_angle of an
+ *   orbm_motion_batch with mp_begin[f] = f * last.kp_cap and kp_begin[f] = f * cur.kp_cap (rows from last.frame_n[f] up:
+ *   mp_valid 0); kp_claimed = 1 on the current frame's padding, 0 elsewhere; the current frame's frame_mappoint[i],
+ *   i < frame_n[f], = -1.  It takes no th: the wider search of :238-239 reuses the outputs.
+ * 5 orbtf_end_frame (src/Tracking.cc:1259-1281, :490-511): n_observations[f][i] = mp_nobs, or -1 for no map point, an
+ *   outlier and the padding; then a map point with mp_nobs < 1 becomes -1, its flag 0; then counts[f] = (close and
+ *   tracked, close and not tracked, KeyFrame::TrackedMapPoints(min_obs[f]) of reference_kf[f]).  Close: 0 < kp_depth <
+ *   th_depth (kp_depth NULL, monocular: both counts 0).  TrackedMapPoints: src/KeyFrame.cc:198-220 (min_obs <= 0 counts every point that is not bad);
+ *   reference_kf[f] = -1 gives 0.  NeedNewKeyFrame's decision stays on the host.
+ * 6 orbtf_drop_outliers (:1309-1313): frame_mappoint = -1 where frame_outlier is set.
+ * 7 orbtf_stereo_points (CreateMapPoints :685-743, CreateMapPointsVO :745-786, StereoInitialization :980-997): the
+ *   pairs (Z, i) with Z = kp_depth > 0 (NaN out, +inf in) in ascending (Z, i) order; ranks 0 .. q are processed, q the
+ *   first rank with Z > th_depth and rank + 1 > 100, or the last.  A processed keypoint whose map point is null or has
+ *   mp_nobs < 1 is created; ORBTF_KEYFRAME sets frame_mappoint to -1 in the second case, ORBTF_VO leaves it and
+ *   unprojects as Frame::UnprojectStereo does; ORBTF_INIT creates every Z > 0 in keypoint order.  created_kp[f][..]
+ *   in creation order, created_xw[f][..][3] = uvZToWorld with the frame's pose, n_created[f], n_processed[f]; the host
+ *   allocates the slots.  One workgroup per frame, the depth bits and a flag byte per keypoint in LDS (5 * kp_cap bytes; a
+ *   keypoint's index is its position), a rank sort.
+ * ---------------------------------------------------------------------------------------- */
+#define ORBTF_MERGE 0
+#define ORBTF_REPLACE 1
+#define ORBTF_DISCARD 0
+#define ORBTF_LOCAL_MAP 1
+#define ORBTF_KEYFRAME 0
+#define ORBTF_VO 1
+#define ORBTF_INIT 2
+#define ORBTF_MAX_LEVELS 32
+
+typedef struct orbtf_frames {
+    int32_t n_frames, kp_cap;      /* kp_cap in [1, ORBM_PROJ_MAX_KP] */
+    const int32_t* frame_n;        /* [F] N */
+    int32_t* frame_mappoint;       /* [F][kp_cap] slots, -1 is null */
+    uint8_t* frame_outlier;        /* [F][kp_cap] */
+    float* pose;                   /* [F][12] Rcw row-major, tcw */
+    const float* camera;           /* [F][5] fx, fy, cx, cy, bf */
+    const float* bounds;           /* [F][4] minx, maxx, miny, maxy */
+    const float* kp_xy;            /* [F][kp_cap][2] keypointsUn pt */
+    const int32_t* kp_octave;      /* [F][kp_cap] */
+    const float* kp_uright;        /* [F][kp_cap] */
+    const float* kp_depth;         /* [F][kp_cap] */
+    const float* kp_angle;         /* [F][kp_cap] */
+    const uint8_t* kp_desc;        /* [F][kp_cap][32] */
+} orbtf_frames;
+
+typedef struct orbtf_map {
+    int32_t n_keyframes, n_mappoints, kf_cap;
+    const float* mp_xw;            /* [M][3] */
+    const uint8_t* mp_bad;         /* [M] */
+    const int32_t* mp_nobs;        /* [M] */
+    int32_t* mp_found;             /* [M] updated by orbtf_finish_pose(ORBTF_LOCAL_MAP): IncreaseFound() */
+    const int32_t* mp_replaced;    /* [M] GetReplaced(), -1 for none */
+    const uint8_t* mp_desc;        /* [M][32] */
+    const int32_t* kf_n;           /* [K] */
+    const int32_t* kf_mappoint;    /* [K][kf_cap] */
+} orbtf_map;
+
+/* The arrays of an orbba_pose_batch plus edge_kp; n_frames * kp_cap rows in the per-edge arrays. */
+typedef struct orbtf_edges {
+    int32_t* edge_begin;           /* [F + 1] */
+    double* pose_R;                /* [F][9] */
+    double* pose_t;                /* [F][3] */
+    double* cam;                   /* [F][5] */
+    double* xw;                    /* [E][3] */
+    double* obs;                   /* [E][3] */
+    double* inv_sigma2;            /* [E] */
+    int32_t* edge_kp;              /* [E] */
+} orbtf_edges;
+
+/* The map-point side of an orbm_motion_batch, stride last.kp_cap, and what the current frames add. */
+typedef struct orbtf_motion {
+    int32_t* motion;               /* [F] */
+    int32_t* kp_begin;             /* [F + 1] f * cur.kp_cap */
+    int32_t* mp_begin;             /* [F + 1] f * last.kp_cap */
+    uint8_t* kp_claimed;           /* [F][cur.kp_cap] */
+    uint8_t* mp_valid;             /* [F][last.kp_cap] */
+    float* mp_proj;                /* [F][last.kp_cap][3] */
+    int32_t* mp_octave;
+    uint8_t* mp_desc;              /* [F][last.kp_cap][32], 16-byte aligned as orbtf_map.mp_desc */
+    uint8_t* mp_has_obs;
+    float* mp_angle;
+} orbtf_motion;
+
+typedef struct orbtf_created {
+    int32_t* created_kp;           /* [F][kp_cap] */
+    float* created_xw;             /* [F][kp_cap][3] */
+    int32_t* n_created;            /* [F] */
+    int32_t* n_processed;          /* [F] */
+} orbtf_created;
+
+/* Device entries: every array in HBM; enqueue only on `stream`, nothing is copied back.  ORB_EINVAL for a NULL array
+ * the entry uses, negative sizes, kp_cap outside [1, ORBM_PROJ_MAX_KP] (so no frame exceeds ORBBA_POSE_MAX_EDGES),
+ * kf_cap or src_cap < 1 where used, n_levels outside [1, ORBTF_MAX_LEVELS], 65536 frames or more, an unknown mode,
+ * last->n_frames != cur->n_frames.  orbtf_pose_edges keeps n_frames counts in a per-thread workspace: its calls must
+ * be stream-ordered. */
+int orbtf_apply_matches_device(const orbtf_frames* fr, int32_t mode, const int32_t* kp_match, const int32_t* src,
+                               int32_t n_rows, int32_t src_cap, const int32_t* src_row, int32_t n_mappoints, void* stream);
+int orbtf_pose_edges_device(const orbtf_frames* fr, const orbtf_map* map, const float* inv_sigma2_table, int32_t n_levels,
+                            const orbtf_edges* out, void* stream);
+int orbtf_finish_pose_device(const orbtf_frames* fr, const orbtf_map* map, int32_t mode, const orbtf_edges* edges,
+                             const orbba_pose_result* result, int32_t localization, int32_t stereo, int32_t* n_inliers,
+                             int32_t* discarded, int32_t* n_discarded, void* stream);
+int orbtf_motion_project_device(const orbtf_frames* cur, const orbtf_frames* last, const orbtf_map* map,
+                                const float* velocity, const float* baseline, int32_t monocular, const orbtf_motion* out,
+                                void* stream);
+int orbtf_end_frame_device(const orbtf_frames* fr, const orbtf_map* map, float th_depth, const int32_t* reference_kf,
+                           const int32_t* min_obs, int32_t* n_observations, int32_t* counts, void* stream);
+int orbtf_drop_outliers_device(const orbtf_frames* fr, void* stream);
+int orbtf_stereo_points_device(const orbtf_frames* fr, const orbtf_map* map, int32_t mode, float th_depth,
+                               const orbtf_created* out, void* stream);
+/* Host entries: every pointer is host memory, synchronous; the updated arrays are written back.  Before anything is
+ * copied, besides the checks above: frame_n in [0, kp_cap]; frame_mappoint, src, mp_replaced, kf_mappoint in
+ * [-1, n_mappoints); kp_match in [-1, src_cap); src_row in [0, n_rows); reference_kf in [-1, n_keyframes); kf_n in
+ * [0, kf_cap]; kp_octave of a keypoint below frame_n in [0, n_levels); edge_begin a CSR within n_frames * kp_cap and
+ * edge_kp in [0, kp_cap).  ORB_EINVAL otherwise. */
+int orbtf_apply_matches(const orbtf_frames* fr, int32_t mode, const int32_t* kp_match, const int32_t* src, int32_t n_rows,
+                        int32_t src_cap, const int32_t* src_row, int32_t n_mappoints, int device);
+int orbtf_pose_edges(const orbtf_frames* fr, const orbtf_map* map, const float* inv_sigma2_table, int32_t n_levels,
+                     const orbtf_edges* out, int device);
+int orbtf_finish_pose(const orbtf_frames* fr, const orbtf_map* map, int32_t mode, const orbtf_edges* edges,
+                      const orbba_pose_result* result, int32_t localization, int32_t stereo, int32_t* n_inliers,
+                      int32_t* discarded, int32_t* n_discarded, int device);
+int orbtf_motion_project(const orbtf_frames* cur, const orbtf_frames* last, const orbtf_map* map, const float* velocity,
+                         const float* baseline, int32_t monocular, const orbtf_motion* out, int device);
+int orbtf_end_frame(const orbtf_frames* fr, const orbtf_map* map, float th_depth, const int32_t* reference_kf,
+                    const int32_t* min_obs, int32_t* n_observations, int32_t* counts, int device);
+int orbtf_drop_outliers(const orbtf_frames* fr, int device);
+int orbtf_stereo_points(const orbtf_frames* fr, const orbtf_map* map, int32_t mode, float th_depth,
+                        const orbtf_created* out, int device);
+
 const char* orb_last_error(void);
 int orb_device_count(void);
 

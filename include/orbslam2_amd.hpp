@@ -890,6 +890,57 @@ private:
     orbtl_map map_;
 };
 
+// Tracking's per-frame state (src/Tracking.cc): frame.mappoints, frame.outlier and the pose of a batch of frames stay in the
+// arrays of orbtf_frames in HBM between LocalMap::TrackLocalMap, the searches and PoseOptimization.  Every method only
+// enqueues on `stream`; the host reads back the per-frame integers it decides on (n_inliers, counts, the created lists).
+class TrackingFrames {
+public:
+    TrackingFrames(const orbtf_frames& frames, const orbtf_map& map) : frames_(frames), map_(map) {}
+
+    // frame.mappoints[i] = source[kp_match[i]]: ORBTF_MERGE behind the local-map search, ORBTF_REPLACE behind the motion and
+    // BoW searches
+    void ApplyMatches(int32_t mode, const int32_t* d_kp_match, const int32_t* d_src, int32_t n_rows, int32_t src_cap,
+                      const int32_t* d_src_row = nullptr, void* stream = nullptr) const {
+        check(orbtf_apply_matches_device(&frames_, mode, d_kp_match, d_src, n_rows, src_cap, d_src_row, map_.n_mappoints, stream),
+              "orbtf_apply_matches_device");
+    }
+    // Optimizer::PoseOptimization(&frame) on the resident state: the gather, the optimiser, the result taken back
+    // (ORBTF_DISCARD: DiscardOutliers; ORBTF_LOCAL_MAP: TrackLocalMap's statistics)
+    void PoseOptimization(const float* d_inv_sigma2, int32_t n_levels, const orbtf_edges& edges, orbba_pose_result result,
+                          int32_t mode, bool localization, bool stereo, int32_t* d_n_inliers, int32_t* d_discarded = nullptr,
+                          int32_t* d_n_discarded = nullptr, void* stream = nullptr) const {
+        check(orbtf_pose_edges_device(&frames_, &map_, d_inv_sigma2, n_levels, &edges, stream), "orbtf_pose_edges_device");
+        const orbba_pose_batch batch{frames_.n_frames, edges.edge_begin, edges.pose_R, edges.pose_t, edges.cam,
+                                     edges.xw,         edges.obs,        edges.inv_sigma2};
+        check(orbba_pose_optimization_device(&batch, &result, stream), "orbba_pose_optimization_device");
+        check(orbtf_finish_pose_device(&frames_, &map_, mode, &edges, &result, localization, stereo, d_n_inliers, d_discarded,
+                                       d_n_discarded, stream),
+              "orbtf_finish_pose_device");
+    }
+    // TrackWithMotionModel's setup; out's arrays become the map-point fields of an orbm_motion_batch
+    void MotionProject(const orbtf_frames& last, const float* d_velocity, const float* d_baseline, bool monocular,
+                       const orbtf_motion& out, void* stream = nullptr) const {
+        check(orbtf_motion_project_device(&frames_, &last, &map_, d_velocity, d_baseline, monocular, &out, stream),
+              "orbtf_motion_project_device");
+    }
+    // the end of Tracking::Update: nobservations_, the clean of visual-odometry matches, NeedNewKeyFrame's three counts
+    void EndFrame(float thDepth, const int32_t* d_reference_kf, const int32_t* d_min_obs, int32_t* d_n_observations,
+                  int32_t* d_counts, void* stream = nullptr) const {
+        check(orbtf_end_frame_device(&frames_, &map_, thDepth, d_reference_kf, d_min_obs, d_n_observations, d_counts, stream),
+              "orbtf_end_frame_device");
+    }
+    void DropOutliers(void* stream = nullptr) const { check(orbtf_drop_outliers_device(&frames_, stream), "orbtf_drop_outliers_device"); }
+    // CreateMapPoints (ORBTF_KEYFRAME), CreateMapPointsVO (ORBTF_VO), StereoInitialization (ORBTF_INIT)
+    void StereoPoints(int32_t mode, float thDepth, const orbtf_created& out, void* stream = nullptr) const {
+        check(orbtf_stereo_points_device(&frames_, &map_, mode, thDepth, &out, stream), "orbtf_stereo_points_device");
+    }
+    const orbtf_frames& frames() const { return frames_; }
+
+private:
+    orbtf_frames frames_;
+    orbtf_map map_;
+};
+
 // Map maintenance (src/MapPoint.cc:341-380, src/KeyFrame.cc:94-119, 235-309): the host owns the arrays of orbmm_graph in
 // HBM; after the map moved on the device (orbba_gba_update_map_device, the essential graph, new points, Fuse) it enqueues
 // UpdateNormalAndDepth for the points and UpdateConnections for the keyframes on the stream the readers follow on

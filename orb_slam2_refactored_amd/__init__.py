@@ -30,6 +30,10 @@ Host mirrors of the reference's interfaces (tiantianxuabc/ORB_SLAM2_Refactored):
                                      GrowObservations, observations.py
   Connected / Propagate / LoopConnections <- LoopCorrector::Correct (src/LoopClosing.cc:546-676) and the edge list of
                                      OptimizeEssentialGraph on the device, loop_correction.py
+  tracking                        <- Tracking's per-frame state between the calls above (src/Tracking.cc:187-255, :490-511,
+                                     :664-786, :808-814, :980-997, :1259-1313; the gather of src/Optimizer.cc:355-411):
+                                     apply_matches, pose_edges, finish_pose, motion_project, end_frame, drop_outliers,
+                                     stereo_points, tracking.py
 All compute runs in liborbslam2_amd.so (HIP kernels behind include/orbslam2_amd.h).
 """
 from .extractor import ORBextractor, KP_DTYPE
@@ -37,6 +41,7 @@ from .matcher import (ORBmatcher, ComputeStereoMatches, Fuse, fuse_device, Searc
                       search_by_projection_sim3_device, SearchBySim3, search_by_sim3_device,
                       ComputeDistinctiveDescriptors, compute_distinctive_descriptors_device)
 from . import optimizer
+from . import tracking
 from .sim3solver import Sim3SolverIterate, sim3solver_iterate_device, make_draws
 from .pnpsolver import PnPsolverIterate, pnpsolver_iterate_device, make_draws as make_pnp_draws
 from .initializer import InitializerInitialize, initializer_initialize_device, make_draws as make_initializer_draws
@@ -59,4 +64,4 @@ __all__ = ["AddKeyFrameObservations", "add_keyframe_observations_device", "FuseA
            "create_new_map_points_device", "InitializerInitialize", "initializer_initialize_device", "make_initializer_draws", "PnPsolverIterate", "pnpsolver_iterate_device", "make_pnp_draws", "Sim3SolverIterate", "sim3solver_iterate_device", "make_draws", "ORBextractor", "ORBmatcher", "ComputeStereoMatches", "Fuse", "fuse_device", "SearchByProjectionSim3",
            "search_by_projection_sim3_device", "SearchBySim3", "search_by_sim3_device", "ComputeDistinctiveDescriptors",
            "compute_distinctive_descriptors_device", "optimizer", "KP_DTYPE", "synth_image", "shifted_pair", "stereo_pair",
-           "make_pose_batch"]
+           "make_pose_batch", "tracking"]

@@ -327,6 +327,35 @@ class OrbtlResult(C.Structure):
                                           "mp_desc", "mp_has_obs", "votes")]
 
 
+class OrbtfFrames(C.Structure):
+    """orbtf_frames (include/orbslam2_amd.h)."""
+    _fields_ = [("n_frames", C.c_int32), ("kp_cap", C.c_int32)] + [
+        (k, C.c_void_p) for k in ("frame_n", "frame_mappoint", "frame_outlier", "pose", "camera", "bounds", "kp_xy", "kp_octave",
+                                  "kp_uright", "kp_depth", "kp_angle", "kp_desc")]
+
+
+class OrbtfMap(C.Structure):
+    """orbtf_map (include/orbslam2_amd.h)."""
+    _fields_ = [("n_keyframes", C.c_int32), ("n_mappoints", C.c_int32), ("kf_cap", C.c_int32)] + [
+        (k, C.c_void_p) for k in ("mp_xw", "mp_bad", "mp_nobs", "mp_found", "mp_replaced", "mp_desc", "kf_n", "kf_mappoint")]
+
+
+class OrbtfEdges(C.Structure):
+    """orbtf_edges (include/orbslam2_amd.h)."""
+    _fields_ = [(k, C.c_void_p) for k in ("edge_begin", "pose_R", "pose_t", "cam", "xw", "obs", "inv_sigma2", "edge_kp")]
+
+
+class OrbtfMotion(C.Structure):
+    """orbtf_motion (include/orbslam2_amd.h)."""
+    _fields_ = [(k, C.c_void_p) for k in ("motion", "kp_begin", "mp_begin", "kp_claimed", "mp_valid", "mp_proj", "mp_octave",
+                                          "mp_desc", "mp_has_obs", "mp_angle")]
+
+
+class OrbtfCreated(C.Structure):
+    """orbtf_created (include/orbslam2_amd.h)."""
+    _fields_ = [(k, C.c_void_p) for k in ("created_kp", "created_xw", "n_created", "n_processed")]
+
+
 class OrbmmPoints(C.Structure):
     """orbmm_points (include/orbslam2_amd.h)."""
     _fields_ = [("n_keyframes", C.c_int32), ("n_mappoints", C.c_int32), ("kf_cap", C.c_int32), ("n_obs", C.c_int32),
@@ -545,6 +574,17 @@ SIGNATURES = {    "orbx_create": (C.c_int, [C.POINTER(OrbxParams), C.c_int, C.PO
     "orbba_essential_graph_edges_device": (C.c_int, [C.POINTER(EssentialGraphTables), C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                                      C.c_int32, VP, VP, VP, VP, VP]),
     "orbx_pack_descriptors": (C.c_int,[VP, C.c_int, VP, VP, C.c_int, VP, C.c_int, VP]),
+    **{name + suffix: (C.c_int, args + [last]) for suffix, last in (("_device", VP), ("", C.c_int)) for name, args in {
+        "orbtf_apply_matches": [C.POINTER(OrbtfFrames), C.c_int32, VP, VP, C.c_int32, C.c_int32, VP, C.c_int32],
+        "orbtf_pose_edges": [C.POINTER(OrbtfFrames), C.POINTER(OrbtfMap), VP, C.c_int32, C.POINTER(OrbtfEdges)],
+        "orbtf_finish_pose": [C.POINTER(OrbtfFrames), C.POINTER(OrbtfMap), C.c_int32, C.POINTER(OrbtfEdges),
+                              C.POINTER(PoseResult), C.c_int32, C.c_int32, VP, VP, VP],
+        "orbtf_motion_project": [C.POINTER(OrbtfFrames), C.POINTER(OrbtfFrames), C.POINTER(OrbtfMap), VP, VP, C.c_int32,
+                                 C.POINTER(OrbtfMotion)],
+        "orbtf_end_frame": [C.POINTER(OrbtfFrames), C.POINTER(OrbtfMap), C.c_float, VP, VP, VP, VP],
+        "orbtf_drop_outliers": [C.POINTER(OrbtfFrames)],
+        "orbtf_stereo_points": [C.POINTER(OrbtfFrames), C.POINTER(OrbtfMap), C.c_int32, C.c_float, C.POINTER(OrbtfCreated)],
+    }.items()},
     "orbx_profile_enable": (C.c_int, [VP, C.c_int]),
     "orbx_profile_read": (C.c_int, [VP, VP, VP]),
     "orbx_debug_level_candidates": (C.c_int, [VP, C.c_int, C.c_int, VP, C.c_int, C.POINTER(C.c_int)]),

@@ -97,11 +97,16 @@ LM_HD void lm_camera_to_image(const LmFrame& f, const float* Xc, float& u, float
     v = invZ * f.fy * Xc[1] + f.cy;
 }
 
-// Rwc (X, Y, Z) + twc of uvZToCamera(u, v, Z) (CameraUnProjection::uvZToWorld)
-LM_HD void lm_uvz_to_world(const LmFrame& f, float u, float v, float Z, float* X) {
-    const float x = f.invfx * (u - f.cx) * Z, y = f.invfy * (v - f.cy) * Z;
+// Rwc (x, y, Z) + twc (CameraUnProjection::CameraToWorld)
+LM_HD void lm_camera_to_world(const LmFrame& f, float x, float y, float Z, float* X) {
 #pragma unroll
     for (int i = 0; i < 3; i++) X[i] = lm_dot3(f.Rwc[3 * i], f.Rwc[3 * i + 1], f.Rwc[3 * i + 2], x, y, Z) + f.Ow[i];
+}
+
+// CameraToWorld of uvZToCamera(u, v, Z) (CameraUnProjection::uvZToWorld)
+LM_HD void lm_uvz_to_world(const LmFrame& f, float u, float v, float Z, float* X) {
+    const float x = f.invfx * (u - f.cx) * Z, y = f.invfy * (v - f.cy) * Z;
+    lm_camera_to_world(f, x, y, Z, X);
 }
 
 LM_HD void lm_kinv(const LmFrame& f, float* Ki) {
