@@ -670,9 +670,11 @@ static bool epipolar_ok(float x1, float y1, float x2, float y2, const float* F, 
 // ---------------------------------------------------------------------------------------------
 struct Quat { double x, y, z, w; };
 
-static Quat quat_from_R(const double* m) {   // Eigen::Quaterniond(const Matrix3d&)
+// branch (may be null): 0 for t > 0, else 1 + i of the largest diagonal element
+static Quat quat_from_R(const double* m, int* branch = nullptr) {   // Eigen::Quaterniond(const Matrix3d&)
     Quat q;
     const double t = m[0] + m[4] + m[8];
+    if (branch) *branch = 0;
     if (t > 0) {
         double s = std::sqrt(t + 1.0);
         q.w = 0.5 * s;
@@ -684,6 +686,7 @@ static Quat quat_from_R(const double* m) {   // Eigen::Quaterniond(const Matrix3
         int i = 0;
         if (m[4] > m[0]) i = 1;
         if (m[8] > m[3 * i + i]) i = 2;
+        if (branch) *branch = 1 + i;
         const int j = (i + 1) % 3, k = (j + 1) % 3;
         double s = std::sqrt(m[3 * i + i] - m[3 * j + j] - m[3 * k + k] + 1.0);
         double qv[3];
@@ -1335,7 +1338,58 @@ struct Vocabulary {
 // PoseOptimization: one SE3 vertex, unary edges (types_six_dof_expmap.h:143-202,
 // types_six_dof_expmap.cpp:266-364), LinearSolverDense under OptimizationAlgorithmLevenberg.
 // ---------------------------------------------------------------------------------------------
+// oracle_pose_optimization_trace's records (tests/oracle_api.py PO_*_DTYPE have the same layouts).  One per
+// LM trial: lambda and cur before the trial, scale with its 1e-3; the iteration-end fields are filled on the
+// trial that closes an iteration (iter_end = 1), nbad after the relative-improvement test where the iteration
+// reached it (nbad_tested).
+struct oracle_po_trial {
+    int32_t frame, round, it, q, ok, accepted;
+    double cur, tmp, scale, rho, lambda;
+    int32_t iter_end, nbad_tested;
+    double ini, cur_end;
+    int32_t nbad, pad;
+};
+enum { PO_END_NONE = 0, PO_END_BUDGET, PO_END_Q10, PO_END_RHO0, PO_END_NBAD };
+// One per round: the optimize() call, then the classification that follows it.  min_margin is the smallest
+// |chi2 - th| / th over the frame's edges (NaN chi2 skipped).
+struct oracle_po_round {
+    int32_t frame, round, n_active, iterations, reason, n_outliers, n_readmitted, pad;
+    double min_margin;
+};
+// One per frame that ran: the branch ToSE3Quat's Quaterniond(R) took (0: trace > 0, 1 + i: largest diagonal
+// i) and whether normalizeRotation flipped the sign (w < 0).
+struct oracle_po_frame { int32_t frame, branch, flipped; };
+
+struct POTrace {
+    oracle_po_trial* trial = nullptr;
+    oracle_po_round* round = nullptr;
+    oracle_po_frame* frame = nullptr;
+    int trial_cap = 0, round_cap = 0, frame_cap = 0;
+    int n_trials = 0, n_rounds = 0, n_frames = 0;   // count past the caps, so the caller sees an overflow
+    int f = 0, k = 0;
+    oracle_po_trial* push_trial() {
+        oracle_po_trial* r = n_trials < trial_cap ? &trial[n_trials] : nullptr;
+        n_trials++;
+        if (r) { std::memset(r, 0, sizeof *r); r->frame = f; r->round = k; }
+        return r;
+    }
+    oracle_po_round* push_round() {
+        oracle_po_round* r = n_rounds < round_cap ? &round[n_rounds] : nullptr;
+        n_rounds++;
+        if (r) { std::memset(r, 0, sizeof *r); r->frame = f; r->round = k; }
+        return r;
+    }
+    oracle_po_frame* push_frame() {
+        oracle_po_frame* r = n_frames < frame_cap ? &frame[n_frames] : nullptr;
+        n_frames++;
+        if (r) { std::memset(r, 0, sizeof *r); r->frame = f; }
+        return r;
+    }
+};
+
 struct PoseOpt {
+    POTrace* trace = nullptr;      // test hook: read-only for the optimisation
+    int end_reason = PO_END_NONE;   // why the last optimize() ended
     int E = 0;
     const double *xw = nullptr, *obs = nullptr, *info = nullptr;
     double fx = 0, fy = 0, cx = 0, cy = 0, bf = 0;
@@ -1448,10 +1502,13 @@ struct PoseOpt {
     }
     // SparseOptimizer::optimize (sparse_optimizer.cpp:354-419) around
     // OptimizationAlgorithmLevenberg::solve (optimization_algorithm_levenberg.cpp:60-163).
-    int optimize(int iters) {
+    // max_trials is g2o's _maxTrialsAfterFailure (10).
+    int optimize(int iters, int max_trials = 10) {
+        end_reason = PO_END_NONE;
         if (act.empty()) return -1;   // "0 vertices to optimize"
         double lambda = 0, ni = 2;
         int nbad = 0, done = 0;
+        oracle_po_trial* tr = nullptr;
         for (int it = 0; it < iters; it++) {
             compute_active_errors();
             double cur = active_robust_chi2();
@@ -1459,12 +1516,14 @@ struct PoseOpt {
             build_system();
             if (it == 0) {   // computeLambdaInit (:166-180), tau 1e-5
                 double m = 0;
-                for (int j = 0; j < 6; j++) m = std::max(m, std::fabs(H[7 * j]));
+                for (int j = 0; j < 6; j++) m = std::max(std::fabs(H[7 * j]), m);   // g2o's argument order: NaN wins
                 lambda = 1e-5 * m; ni = 2; nbad = 0;
             }
             double rho = 0;
             int q = 0;
             do {
+                tr = trace ? trace->push_trial() : nullptr;
+                if (tr) { tr->it = it; tr->q = q; tr->lambda = lambda; tr->cur = cur; }
                 const SE3 saved = pose;
                 const bool ok = solve(lambda);
                 if (!ok) std::memset(x, 0, sizeof(x));   // x left unspecified by a failed solve
@@ -1480,6 +1539,10 @@ struct PoseOpt {
                     scale += s;
                 }
                 rho /= scale;
+                if (tr) {
+                    tr->ok = ok; tr->tmp = tmp; tr->scale = scale; tr->rho = rho;
+                    tr->accepted = rho > 0 && std::isfinite(tmp);
+                }
                 if (rho > 0 && std::isfinite(tmp)) {
                     double alpha = 1. - std::pow((2 * rho - 1), 3);
                     alpha = std::min(alpha, 2. / 3.);
@@ -1492,11 +1555,14 @@ struct PoseOpt {
                     pose = saved;
                 }
                 q++;
-            } while (rho < 0 && q < 10);
+            } while (rho < 0 && q < max_trials);
             done++;
-            if (q == 10 || rho == 0) break;
+            if (tr) { tr->iter_end = 1; tr->ini = ini; tr->cur_end = cur; tr->nbad = nbad; }
+            end_reason = PO_END_BUDGET;   // (until something below says otherwise)
+            if (q == max_trials || rho == 0) { end_reason = q == max_trials ? PO_END_Q10 : PO_END_RHO0; break; }
             if ((ini - cur) * 1e3 < ini) nbad++; else nbad = 0;
-            if (nbad >= 3) break;
+            if (tr) { tr->nbad_tested = 1; tr->nbad = nbad; }
+            if (nbad >= 3) { end_reason = PO_END_NBAD; break; }
         }
         return done;
     }
@@ -2454,7 +2520,10 @@ int oracle_search_for_initialization(const orbm_init_batch* b, int32_t* matches1
 }
 
 // Optimizer::PoseOptimization (src/Optimizer.cc:345-489), frame by frame.
-int oracle_pose_optimization(const orbba_pose_batch* in, orbba_pose_result* out) {
+// trace (may be null) receives the records; max_iters / max_trials are optimize()'s budget and g2o's
+// _maxTrialsAfterFailure (both 10 in the reference; other values are a test's what-if).
+static int pose_optimization_run(const orbba_pose_batch* in, orbba_pose_result* out, POTrace* trace, int max_iters,
+                                 int max_trials) {
     const double maxChi2[2] = {5.991, 7.815};   // CHI2_MONO, CHI2_STEREO (:44-45)
     for (int f = 0; f < in->n_frames; f++) {
         const int e0 = in->edge_begin[f], E = in->edge_begin[f + 1] - e0;
@@ -2468,6 +2537,8 @@ int oracle_pose_optimization(const orbba_pose_batch* in, orbba_pose_result* out)
             continue;
         }
         PoseOpt po;
+        po.trace = trace;
+        if (trace) trace->f = f;
         po.E = E;
         po.xw = in->xw + 3 * (size_t)e0; po.obs = in->obs + 3 * (size_t)e0; po.info = in->inv_sigma2 + e0;
         const double* c = in->cam + 5 * (size_t)f;
@@ -2477,7 +2548,12 @@ int oracle_pose_optimization(const orbba_pose_batch* in, orbba_pose_result* out)
         po.level.assign(E, 0);
         po.err.assign(3 * (size_t)E, 0);
         SE3 init;   // ToSE3Quat(frame->pose)
-        init.q = quat_from_R(R0);
+        int branch = 0;
+        init.q = quat_from_R(R0, &branch);
+        if (trace) {
+            oracle_po_frame* fr = trace->push_frame();
+            if (fr) { fr->branch = branch; fr->flipped = init.q.w < 0; }
+        }
         quat_normalize_pos(init.q);
         for (int k = 0; k < 3; k++) init.t[k] = t0[k];
         int noutliers = 0;
@@ -2485,16 +2561,30 @@ int oracle_pose_optimization(const orbba_pose_batch* in, orbba_pose_result* out)
             po.pose = init;
             po.act.clear();   // initializeOptimization(0)
             for (int e = 0; e < E; e++) if (po.level[e] == 0) po.act.push_back(e);
-            po.optimize(10);
+            if (trace) trace->k = k;
+            const int done = po.optimize(max_iters, max_trials);
+            oracle_po_round* rr = trace ? trace->push_round() : nullptr;
+            if (rr) {
+                rr->n_active = (int)po.act.size(); rr->iterations = done < 0 ? 0 : done; rr->reason = po.end_reason;
+                rr->min_margin = HUGE_VAL;
+            }
             noutliers = 0;
             for (int e = 0; e < E; e++) {
-                if (out->outlier[e0 + e]) po.compute_error(e);
-                if (po.chi2(e) > maxChi2[po.stereo[e]]) {
+                const bool was = out->outlier[e0 + e];
+                if (was) po.compute_error(e);
+                const double c = po.chi2(e), th = maxChi2[po.stereo[e]];
+                if (rr) {
+                    const double m = std::fabs(c - th) / th;
+                    if (m < rr->min_margin) rr->min_margin = m;
+                }
+                if (c > th) {
                     out->outlier[e0 + e] = 1; po.level[e] = 1; noutliers++;
                 } else {
                     out->outlier[e0 + e] = 0; po.level[e] = 0;
+                    if (rr && was) rr->n_readmitted++;
                 }
             }
+            if (rr) rr->n_outliers = noutliers;
             if (k == 2) po.robust = false;   // setRobustKernel(0)
             if (E < 10) break;               // optimizer.edges().size() < 10
         }
@@ -2503,6 +2593,24 @@ int oracle_pose_optimization(const orbba_pose_batch* in, orbba_pose_result* out)
         out->n_inliers[f] = E - noutliers;
     }
     return 0;
+}
+
+int oracle_pose_optimization(const orbba_pose_batch* in, orbba_pose_result* out) {
+    return pose_optimization_run(in, out, nullptr, 10, 10);
+}
+
+// The same run with its records written to the caller's arrays (caps in records).  n_out[3] receives the
+// numbers of trial, round and frame records (more than a cap: that array was too short).
+int oracle_pose_optimization_trace(const orbba_pose_batch* in, orbba_pose_result* out, int max_iters, int max_trials,
+                                   oracle_po_trial* trials, int trial_cap, oracle_po_round* rounds, int round_cap,
+                                   oracle_po_frame* frames, int frame_cap, int32_t* n_out) {
+    POTrace t;
+    t.trial = trials; t.trial_cap = trial_cap;
+    t.round = rounds; t.round_cap = round_cap;
+    t.frame = frames; t.frame_cap = frame_cap;
+    const int rc = pose_optimization_run(in, out, &t, max_iters, max_trials);
+    n_out[0] = t.n_trials; n_out[1] = t.n_rounds; n_out[2] = t.n_frames;
+    return rc;
 }
 
 // std::sort of QuadTreeSuppression's DivisibleNode vector (src/ORBextractor.cc:635-643), real

@@ -408,8 +408,29 @@ class PoseResult(C.Structure):
     _fields_ = [("pose_R", C.c_void_p), ("pose_t", C.c_void_p), ("n_inliers", C.c_void_p), ("outlier", C.c_void_p)]
 
 
-def pose_optimization(batch):
-    """Optimizer::PoseOptimization (src/Optimizer.cc:345-489) per frame of a make_pose_batch dict."""
+# oracle_po_trial / oracle_po_round / oracle_po_frame (oracle/orb_oracle.cpp).  Trial: lambda / cur are the
+# values before the trial, scale includes its 1e-3; ini / cur_end / nbad are filled on the trial that closes an
+# iteration (iter_end), nbad after the relative-improvement test where the iteration reached it (nbad_tested).
+# Round: optimize() and the classification after it; reason indexes PO_END_REASONS; min_margin is the smallest
+# |chi2 - th| / th over the frame's edges.  Frame: Quaterniond(R)'s branch (PO_QUAT_BRANCHES) and whether
+# normalizeRotation flipped the sign; frames with fewer than 3 edges leave no record.
+PO_TRIAL_DTYPE = np.dtype([("frame", "<i4"), ("round", "<i4"), ("it", "<i4"), ("q", "<i4"), ("ok", "<i4"),
+                           ("accepted", "<i4"), ("cur", "<f8"), ("tmp", "<f8"), ("scale", "<f8"), ("rho", "<f8"),
+                           ("lambda", "<f8"), ("iter_end", "<i4"), ("nbad_tested", "<i4"), ("ini", "<f8"),
+                           ("cur_end", "<f8"), ("nbad", "<i4"), ("pad", "<i4")])
+PO_ROUND_DTYPE = np.dtype([("frame", "<i4"), ("round", "<i4"), ("n_active", "<i4"), ("iterations", "<i4"),
+                           ("reason", "<i4"), ("n_outliers", "<i4"), ("n_readmitted", "<i4"), ("pad", "<i4"),
+                           ("min_margin", "<f8")])
+PO_FRAME_DTYPE = np.dtype([("frame", "<i4"), ("branch", "<i4"), ("flipped", "<i4")])
+PO_END_REASONS = ("none", "budget", "q10", "rho0", "nbad")   # "none": no active edge
+PO_QUAT_BRANCHES = ("t", "i0", "i1", "i2")
+
+
+def pose_optimization(batch, trace=False, max_iters=10, max_trials=10):
+    """Optimizer::PoseOptimization (src/Optimizer.cc:345-489) per frame of a make_pose_batch dict.
+    trace=True: the same run through oracle_pose_optimization_trace; the result also has "trials", "rounds"
+    and "frames" (PO_*_DTYPE records).  max_iters / max_trials (trace only) are optimize()'s budget and g2o's
+    maxTrialsAfterFailure: other values than the reference's 10 answer a test's what-if."""
     keep = _Keep()
     n = len(batch["edge_begin"]) - 1
     E = int(batch["edge_begin"][-1])
@@ -419,7 +440,19 @@ def pose_optimization(batch):
     out = dict(pose_R=np.zeros((n, 9)), pose_t=np.zeros((n, 3)), n_inliers=np.zeros(n, np.int32),
                outlier=np.zeros(E, np.uint8))
     res = PoseResult(ptr(out["pose_R"]), ptr(out["pose_t"]), ptr(out["n_inliers"]), ptr(out["outlier"]))
-    lib().oracle_pose_optimization(C.byref(pb), C.byref(res))
+    if not trace:
+        assert max_iters == 10 and max_trials == 10, "max_iters / max_trials need trace=True"
+        lib().oracle_pose_optimization(C.byref(pb), C.byref(res))
+        return out
+    assert (PO_TRIAL_DTYPE.itemsize, PO_ROUND_DTYPE.itemsize, PO_FRAME_DTYPE.itemsize) == (96, 40, 12)
+    trials = np.zeros(max(n, 1) * 4 * max_iters * max_trials, PO_TRIAL_DTYPE)
+    rounds = np.zeros(max(n, 1) * 4, PO_ROUND_DTYPE)
+    frames = np.zeros(max(n, 1), PO_FRAME_DTYPE)
+    cnt = np.zeros(3, np.int32)
+    lib().oracle_pose_optimization_trace(C.byref(pb), C.byref(res), int(max_iters), int(max_trials), ptr(trials),
+                                         len(trials), ptr(rounds), len(rounds), ptr(frames), len(frames), ptr(cnt))
+    assert cnt[0] <= len(trials) and cnt[1] <= len(rounds) and cnt[2] <= len(frames), cnt
+    out["trials"], out["rounds"], out["frames"] = trials[:cnt[0]].copy(), rounds[:cnt[1]].copy(), frames[:cnt[2]].copy()
     return out
 
 
