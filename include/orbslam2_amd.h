@@ -2430,6 +2430,85 @@ int orbtf_drop_outliers(const orbtf_frames* fr, int device);
 int orbtf_stereo_points(const orbtf_frames* fr, const orbtf_map* map, int32_t mode, float th_depth,
                         const orbtf_created* out, int device);
 
+/* ------------------------------------------------------------------------------------------
+ * Frame construction (src/System.cc): what the reference does between Extract and the Frame constructor, on the
+ * extractor's HBM-resident output, batched over frames.  UndistortKeyPoints (:153-174, called at :455, :512, :570),
+ * depth.convertTo + ComputeStereoFromRGBD (:515-516, :197-219), ComputeImageBounds (:177-194) and the split of cv::KeyPoint
+ * into the arrays orbtf_frames, orbtl_frames and the projection batches take.  Per-element arithmetic: csrc/fr_undistort.h.
+ *
+ * Input: kps [F][kp_cap] and counts [F] exactly as orbx_extract_batch_device writes them with cap == kp_cap; camera [F][5]
+ * = fx, fy, cx, cy, bf (orbtf_frames.camera); dist [F][5] = k1, k2, p1, p2, k3 (four coefficients: k3 = 0).  A device-side
+ * count is clamped to [0, kp_cap].
+ *   undistortion   cv::undistortPoints(points, points, K, distCoeffs, cv::Mat(), K) restated [ext, recalled]: double
+ *                  arithmetic, exactly 5 fixed-point iterations, one rounding to float per coordinate.  icdist < 0 leaves
+ *                  the loop with the first guess, as newer OpenCV does (parity unpinned).  k1 == 0.f copies the keypoints
+ *                  bit for bit and gives the bounds (0, cols, 0, rows) (:155, :182).
+ *   ORBFR_RGBD     v = (int)pt.y, u = (int)pt.x of the distorted keypoint, d = depth(v, u) * depth_factor in float (the
+ *                  convertTo folded into the lookup: uint16 or float elements, frame f at depth + f * depth_frame_stride
+ *                  bytes, rows depth_step bytes apart); d > 0: kp_depth = d, kp_uright = xUn - bf / d; else both -1 (NaN,
+ *                  zeros, negatives; +inf is positive).  A coordinate that is NaN or outside the image gives -1 / -1 (a
+ *                  departure: the reference reads outside the depth map; extractor output never does).
+ *   ORBFR_MONO     kp_uright = kp_depth = -1.
+ *   ORBFR_STEREO   kp_uright / kp_depth are not touched: the caller points them at orbx_stereo_matches_batch_device's
+ *                  outputs (src/System.cc:455-461).
+ * Output, stride kp_cap, each pointer optional (NULL: not written): frame_n = the clamped count, kp_xy / kp_octave /
+ * kp_angle, kp_un = the full undistorted records (keypointsUn, the kf_keypoint form of orblm_batch and orbba_window_map;
+ * it may be kps itself), kp_uright / kp_depth, bounds [F][4] = minx, maxx, miny, maxy, frame_mappoint = -1,
+ * frame_outlier = 0, kp_begin [F + 1] = f * kp_cap.  Rows from frame_n[f] up are padding and stay as they were.
+ * Descriptors are not touched: the extractor's d_desc already is kp_desc.  Frames are independent; no atomics: two runs
+ * are byte-identical.  Reference quirk: TrackMonocular never computes imageBounds_; a caller reproducing
+ * that passes bounds = NULL and its own array to the searches.
+ * ---------------------------------------------------------------------------------------- */
+#define ORBFR_MONO 0
+#define ORBFR_STEREO 1
+#define ORBFR_RGBD 2
+#define ORBFR_DEPTH_U16 0
+#define ORBFR_DEPTH_F32 1
+
+typedef struct orbfr_input {
+    int32_t n_frames, kp_cap;      /* kp_cap in [1, ORBM_PROJ_MAX_KP] */
+    int32_t rows, cols;            /* the image, at least 1 x 1 */
+    int32_t mode;                  /* ORBFR_MONO, ORBFR_STEREO, ORBFR_RGBD */
+    int32_t depth_type;            /* ORBFR_DEPTH_U16, ORBFR_DEPTH_F32 (ORBFR_RGBD only, as the four fields below) */
+    const orbx_keypoint* kps;      /* [F][kp_cap] */
+    const int32_t* counts;         /* [F] */
+    const float* camera;           /* [F][5] fx, fy, cx, cy, bf */
+    const float* dist;             /* [F][5] k1, k2, p1, p2, k3 */
+    const void* depth;             /* F depth images of rows x cols elements */
+    size_t depth_frame_stride;     /* bytes between frames */
+    size_t depth_step;             /* bytes between rows: at least cols elements, a multiple of the element size */
+    float depth_factor;            /* depthFactor_ (1 / DepthMapFactor) */
+} orbfr_input;
+
+typedef struct orbfr_frames {
+    int32_t* frame_n;              /* [F] */
+    float* kp_xy;                  /* [F][kp_cap][2] keypointsUn pt */
+    int32_t* kp_octave;            /* [F][kp_cap] */
+    float* kp_angle;               /* [F][kp_cap] */
+    orbx_keypoint* kp_un;          /* [F][kp_cap] keypointsUn */
+    float* kp_uright;              /* [F][kp_cap] */
+    float* kp_depth;               /* [F][kp_cap] */
+    float* bounds;                 /* [F][4] */
+    int32_t* frame_mappoint;       /* [F][kp_cap] */
+    uint8_t* frame_outlier;        /* [F][kp_cap] */
+    int32_t* kp_begin;             /* [F + 1] */
+} orbfr_frames;
+
+/* Device entry: every array in HBM; one launch enqueued on `stream`, nothing is copied back.  ORB_EINVAL for a NULL struct,
+ * a NULL kps, counts, camera or dist (depth in ORBFR_RGBD), negative n_frames or 65536 frames or more, kp_cap outside
+ * [1, ORBM_PROJ_MAX_KP], rows or cols below 1, an unknown mode or depth type, a depth_step below cols elements or not a
+ * multiple of the element size, a depth_frame_stride that is not such a multiple or (more than one frame) shorter than a
+ * frame, a depth pointer not aligned to its element. */
+int orbfr_build_frames_device(const orbfr_input* in, const orbfr_frames* out, void* stream);
+/* Host entry: every pointer is host memory, synchronous; the requested outputs are written back.  Before anything is
+ * copied, besides the checks above: counts in [0, kp_cap].  ORB_EINVAL otherwise. */
+int orbfr_build_frames(const orbfr_input* in, const orbfr_frames* out, int device);
+/* Plain CPU functions of the same arithmetic, for the reference's own once-per-run shape (imageBounds_ is computed for
+ * the first frame only, src/System.cc:464-465, :519-520).  camera: fx, fy, cx, cy; dist: k1, k2, p1, p2, k3; bounds: minx,
+ * maxx, miny, maxy.  orbfr_undistort_points is UndistortKeyPoints on n points (x, y) (out may be xy). */
+int orbfr_image_bounds(int32_t rows, int32_t cols, const float* camera, const float* dist, float* bounds);
+int orbfr_undistort_points(const float* camera, const float* dist, const float* xy, int32_t n, float* out);
+
 const char* orb_last_error(void);
 int orb_device_count(void);
 

@@ -941,6 +941,49 @@ private:
     orbtf_map map_;
 };
 
+// What System does between Extract and the Frame constructor (src/System.cc:153-219, :455, :512-520, :570) on the
+// extractor's HBM-resident output: undistortion, RGB-D depth, image bounds and the split into the frame tables.  The
+// builder holds the tables it writes as an orbtf_frames, so TrackingFrames(builder.frames(), map) is the next step with
+// nothing copied; pose and kp_desc (the extractor's d_desc) are the caller's.  Build only enqueues on `stream`.
+class FrameBuilder {
+public:
+    // tables: frame_n, frame_mappoint, frame_outlier, bounds, kp_xy, kp_octave, kp_uright, kp_depth and kp_angle are written
+    // (a NULL one is skipped; ORBFR_STEREO leaves kp_uright / kp_depth to orbx_stereo_matches_batch_device), camera is read.
+    // d_dist [F][5] = k1, k2, p1, p2, k3.  d_kp_un / d_kp_begin: keypointsUn records and f * kp_cap, or NULL.
+    FrameBuilder(const orbtf_frames& tables, const float* d_dist, int rows, int cols, orbx_keypoint* d_kp_un = nullptr,
+                 int32_t* d_kp_begin = nullptr)
+        : frames_(tables), dist_(d_dist), rows_(rows), cols_(cols), kp_un_(d_kp_un), kp_begin_(d_kp_begin) {}
+
+    // TrackMonocular (:570) and TrackStereo (:455): d_kps / d_counts are orbx_extract_batch_device's with cap == kp_cap
+    void Build(int32_t mode, const orbx_keypoint* d_kps, const int32_t* d_counts, void* stream = nullptr) const {
+        Build(mode, d_kps, d_counts, nullptr, 0, 0, 0, 0.f, stream);
+    }
+    // TrackRGBD (:512-520): depth images of depth_type elements, depth_factor = depthFactor_
+    void Build(int32_t mode, const orbx_keypoint* d_kps, const int32_t* d_counts, const void* d_depth, int32_t depth_type,
+               size_t depth_frame_stride, size_t depth_step, float depth_factor, void* stream = nullptr) const {
+        const orbfr_input in{frames_.n_frames, frames_.kp_cap, rows_,   cols_,   mode,
+                             depth_type,       d_kps,          d_counts, frames_.camera, dist_,
+                             d_depth,          depth_frame_stride, depth_step, depth_factor};
+        const orbfr_frames out{const_cast<int32_t*>(frames_.frame_n), const_cast<float*>(frames_.kp_xy),
+                               const_cast<int32_t*>(frames_.kp_octave), const_cast<float*>(frames_.kp_angle), kp_un_,
+                               const_cast<float*>(frames_.kp_uright), const_cast<float*>(frames_.kp_depth),
+                               const_cast<float*>(frames_.bounds), frames_.frame_mappoint, frames_.frame_outlier, kp_begin_};
+        check(orbfr_build_frames_device(&in, &out, stream), "orbfr_build_frames_device");
+    }
+    // ComputeImageBounds on the CPU, for the reference's once-per-run shape (:464-465): minx, maxx, miny, maxy
+    static void ImageBounds(int rows, int cols, const float* camera, const float* dist, float bounds[4]) {
+        check(orbfr_image_bounds(rows, cols, camera, dist, bounds), "orbfr_image_bounds");
+    }
+    const orbtf_frames& frames() const { return frames_; }
+
+private:
+    orbtf_frames frames_;
+    const float* dist_;
+    int rows_, cols_;
+    orbx_keypoint* kp_un_;
+    int32_t* kp_begin_;
+};
+
 // Map maintenance (src/MapPoint.cc:341-380, src/KeyFrame.cc:94-119, 235-309): the host owns the arrays of orbmm_graph in
 // HBM; after the map moved on the device (orbba_gba_update_map_device, the essential graph, new points, Fuse) it enqueues
 // UpdateNormalAndDepth for the points and UpdateConnections for the keyframes on the stream the readers follow on

@@ -34,6 +34,9 @@ Host mirrors of the reference's interfaces (tiantianxuabc/ORB_SLAM2_Refactored):
                                      :664-786, :808-814, :980-997, :1259-1313; the gather of src/Optimizer.cc:355-411):
                                      apply_matches, pose_edges, finish_pose, motion_project, end_frame, drop_outliers,
                                      stereo_points, tracking.py
+  frame                           <- what System does between Extract and the Frame constructor (src/System.cc:153-219):
+                                     UndistortKeyPoints, ComputeImageBounds, depth.convertTo + ComputeStereoFromRGBD and the
+                                     split of cv::KeyPoint into tracking's arrays: build, build_device, frame.py
 All compute runs in liborbslam2_amd.so (HIP kernels behind include/orbslam2_amd.h).
 """
 from .extractor import ORBextractor, KP_DTYPE
@@ -42,6 +45,7 @@ from .matcher import (ORBmatcher, ComputeStereoMatches, Fuse, fuse_device, Searc
                       ComputeDistinctiveDescriptors, compute_distinctive_descriptors_device)
 from . import optimizer
 from . import tracking
+from . import frame
 from .sim3solver import Sim3SolverIterate, sim3solver_iterate_device, make_draws
 from .pnpsolver import PnPsolverIterate, pnpsolver_iterate_device, make_draws as make_pnp_draws
 from .initializer import InitializerInitialize, initializer_initialize_device, make_draws as make_initializer_draws
@@ -64,4 +68,4 @@ __all__ = ["AddKeyFrameObservations", "add_keyframe_observations_device", "FuseA
            "create_new_map_points_device", "InitializerInitialize", "initializer_initialize_device", "make_initializer_draws", "PnPsolverIterate", "pnpsolver_iterate_device", "make_pnp_draws", "Sim3SolverIterate", "sim3solver_iterate_device", "make_draws", "ORBextractor", "ORBmatcher", "ComputeStereoMatches", "Fuse", "fuse_device", "SearchByProjectionSim3",
            "search_by_projection_sim3_device", "SearchBySim3", "search_by_sim3_device", "ComputeDistinctiveDescriptors",
            "compute_distinctive_descriptors_device", "optimizer", "KP_DTYPE", "synth_image", "shifted_pair", "stereo_pair",
-           "make_pose_batch", "tracking"]
+           "make_pose_batch", "tracking", "frame"]

@@ -356,6 +356,19 @@ class OrbtfCreated(C.Structure):
     _fields_ = [(k, C.c_void_p) for k in ("created_kp", "created_xw", "n_created", "n_processed")]
 
 
+class OrbfrInput(C.Structure):
+    """orbfr_input (include/orbslam2_amd.h)."""
+    _fields_ = [(k, C.c_int32) for k in ("n_frames", "kp_cap", "rows", "cols", "mode", "depth_type")] + [
+        (k, C.c_void_p) for k in ("kps", "counts", "camera", "dist", "depth")] + [
+        ("depth_frame_stride", C.c_size_t), ("depth_step", C.c_size_t), ("depth_factor", C.c_float)]
+
+
+class OrbfrFrames(C.Structure):
+    """orbfr_frames (include/orbslam2_amd.h)."""
+    _fields_ = [(k, C.c_void_p) for k in ("frame_n", "kp_xy", "kp_octave", "kp_angle", "kp_un", "kp_uright", "kp_depth", "bounds",
+                                          "frame_mappoint", "frame_outlier", "kp_begin")]
+
+
 class OrbmmPoints(C.Structure):
     """orbmm_points (include/orbslam2_amd.h)."""
     _fields_ = [("n_keyframes", C.c_int32), ("n_mappoints", C.c_int32), ("kf_cap", C.c_int32), ("n_obs", C.c_int32),
@@ -585,6 +598,10 @@ SIGNATURES = {    "orbx_create": (C.c_int, [C.POINTER(OrbxParams), C.c_int, C.PO
         "orbtf_drop_outliers": [C.POINTER(OrbtfFrames)],
         "orbtf_stereo_points": [C.POINTER(OrbtfFrames), C.POINTER(OrbtfMap), C.c_int32, C.c_float, C.POINTER(OrbtfCreated)],
     }.items()},
+    "orbfr_build_frames_device": (C.c_int, [C.POINTER(OrbfrInput), C.POINTER(OrbfrFrames), VP]),
+    "orbfr_build_frames": (C.c_int, [C.POINTER(OrbfrInput), C.POINTER(OrbfrFrames), C.c_int]),
+    "orbfr_image_bounds": (C.c_int, [C.c_int32, C.c_int32, VP, VP, VP]),
+    "orbfr_undistort_points": (C.c_int, [VP, VP, VP, C.c_int32, VP]),
     "orbx_profile_enable": (C.c_int, [VP, C.c_int]),
     "orbx_profile_read": (C.c_int, [VP, VP, VP]),
     "orbx_debug_level_candidates": (C.c_int, [VP, C.c_int, C.c_int, VP, C.c_int, C.POINTER(C.c_int)]),
