@@ -2316,8 +2316,8 @@ int orbba_essential_graph_edges_device(const orbba_eg_tables* g, int32_t n_loop_
  *   first rank with Z > th_depth and rank + 1 > 100, or the last.  A processed keypoint whose map point is null or has
  *   mp_nobs < 1 is created; ORBTF_KEYFRAME sets frame_mappoint to -1 in the second case, ORBTF_VO leaves it and
  *   unprojects as Frame::UnprojectStereo does; ORBTF_INIT creates every Z > 0 in keypoint order.  created_kp[f][..]
- *   in creation order, created_xw[f][..][3] = uvZToWorld with the frame's pose, n_created[f], n_processed[f]; the host
- *   allocates the slots.  One workgroup per frame, the depth bits and a flag byte per keypoint in LDS (5 * kp_cap bytes; a
+ *   in creation order, created_xw[f][..][3] = uvZToWorld with the frame's pose, n_created[f], n_processed[f];
+ *   orbmk_create_points (Map creation, below) reads the lists in place and allocates the slots.  One workgroup per frame, the depth bits and a flag byte per keypoint in LDS (5 * kp_cap bytes; a
  *   keypoint's index is its position), a rank sort.
  * ---------------------------------------------------------------------------------------- */
 #define ORBTF_MERGE 0
@@ -2508,6 +2508,177 @@ int orbfr_build_frames(const orbfr_input* in, const orbfr_frames* out, int devic
  * maxx, miny, maxy.  orbfr_undistort_points is UndistortKeyPoints on n points (x, y) (out may be xy). */
 int orbfr_image_bounds(int32_t rows, int32_t cols, const float* camera, const float* dist, float* bounds);
 int orbfr_undistort_points(const float* camera, const float* dist, const float* xy, int32_t n, float* out);
+
+/* ------------------------------------------------------------------------------------------
+ * Map creation: the two places where the map grows, in place on the tables above.  KeyFrame::KeyFrame(const Frame&, ...)
+ * (src/KeyFrame.cc:51-64) and MapPoint::MapPoint(Xw, referenceKF, map) (src/MapPoint.cc:44-56) with the calls that follow
+ * a construction: AddObservation, ComputeDistinctiveDescriptors, KeyFrame::AddMapPoint, Map::AddMapPoint and the frame's
+ * own pointer (src/Tracking.cc:724-736, :981-997, :1104-1126; src/LocalMapping.cc:562-575).  Per-element rules:
+ * csrc/mk_create.h.  Integers and copied float bits only; no atomics: two runs are byte-identical.  The KeyFrame* <->
+ * slot table, NeedNewKeyFrame's decision and the choice of a keyframe's slot stay on the host.  A slot or an index read
+ * from device memory is not trusted: one outside its table is skipped, and no store leaves a table.
+ *
+ * orbmk_insert_keyframes: item i = (item_frame[i], item_kf[i], item_id[i], item_baseline[i]) fills keyframe row k =
+ * item_kf[i] from frame f = item_frame[i] of an orbtf_frames / orbfr_frames batch.  For j < frame_n[f] (clamped to
+ * [0, kp_cap]): kf_mappoint = frame_mappoint (outliers included, as mappoints_(frame.mappoints) copies them), kf_keypoint
+ * = kp_un, kf_kp_octave, kf_uright, kf_depth, kf_desc = kp_desc.  Rows from frame_n[f] up to kf_cap: kf_mappoint = -1,
+ * the other per-keypoint arrays are left as they are.  kf_n = the clamped count, kf_pose = pose (SetPose), kf_camera =
+ * camera[5] and the item's baseline, kf_id = the item's id, kf_bad = kf_not_erase = kf_to_be_erased = 0, kf_parent = -1,
+ * kf_first_connection = 1, n_conn = n_ord = 0, the four connection rows slot -1 / weight 0 up to conn_cap, kf_covis = -1.
+ * Every pointer of orbmk_keyframes is optional (NULL: not written); the frame array behind a table that is written is
+ * required, as are item_id with kf_id and item_baseline with kf_camera.  kp_cap <= kf_cap.  An item whose frame or slot
+ * is outside its table is skipped.  Two items with one slot: the host form refuses them; on the device form the result
+ * is unspecified, but every store stays inside its table.  One launch, a grid over (item, keypoint).
+ *
+ * orbmk_create_points: a list batch.  Item i has the keyframes kf1[i] and kf2[i] (kf2 NULL or kf2[i] = -1: one
+ * observation) and the entries j < n_list[i] (clamped to [0, list_cap]) idx1[i][j], idx2[i][j], rows list_cap apart.
+ * The values xw [..][3] and the optional normal [..][3], max_distance, min_distance of entry (i, j) are at row i *
+ * list_cap + j, or at row i * list_cap + idx1[i][j] with values_by_keypoint.  This reads both producers in place:
+ *   orbtf_created     kf1 = the new keyframe's slot, idx1 = created_kp, xw = created_xw, n_list = n_created, list_cap =
+ *                     kp_cap, one observation; item_frame = the frame, so that frame_mappoint gets the slot (:735, :996);
+ *   orblm_points      one item per plan entry, rounds in order: idx1 = new_idx1, idx2 = new_idx2, n_list = n_created, xw,
+ *                     normal, max_distance, min_distance by keypoint, list_cap = cap1;
+ *   the monocular initial map (:1104-1126): kf1 = the current keyframe (the points' reference keyframe), kf2 = the
+ *                     initial one, list position i = keypoint i of the initial keyframe: idx2[i] = i, idx1[i] =
+ *                     initMatches[i] or -1 where nothing was triangulated, xw = the initializer's p3d by position.
+ * An entry is valid when its keyframe slot(s) are inside the table, 0 <= idx1 < kf_n[kf1], 0 <= idx2 < kf_n[kf2] where
+ * there is a second keyframe, kf1 != kf2, and with values_by_keypoint idx1 < list_cap.  An invalid entry is dropped:
+ * created[i][j] = -1, and it takes no slot.
+ * Allocation.  alloc[0] (HBM, clamped to [0, n_mappoints]) is the number of map-point slots in use.  The caller keeps
+ * the slots [alloc[0], n_mappoints) free: mp_bad = 1, mp_nobs = 0, rows that hold only -1; a free slot's row
+ * [mp_obs_off[p], mp_obs_off[p + 1]) is what the caller provisioned (orbmm_grow_observations' extra); mp_obs_off is
+ * never rewritten.  The valid entries are numbered in creation order, items ascending and list positions ascending, and
+ * number r takes slot alloc[0] + r: the reference's nextId order.  A count per 256 list positions, one scan, the fill.
+ * Everything is checked before anything is written.  The call fails whole when the total does not fit n_mappoints, when
+ * a slot it would take has a row shorter than its observations, or when the batch does not fit recent: status[0] =
+ * ORBMK_OVERFLOW, needed[0] = the slot count required (alloc[0] + the valid entries), needed[1] = the first slot whose
+ * row is too short, or -1 (also when the total does not fit); no table changes, alloc[0] and n_recent[0] stay, created
+ * is -1 and n_created 0.  Otherwise status[0] = ORBMK_OK, needed = (the new alloc[0], -1) and alloc[0] advances.
+ * Per created point p: mp_xw = the given point; mp_normal and mp_max_min = the given values (max, min), zeros where not
+ * given: the constructor's state, to be followed by orbmm_update_normal_depth_device over `created`; mp_bad = 0,
+ * mp_replaced = -1, mp_found = mp_visible = 1, mp_first_kf_id = kf_id[kf1], mp_ref_kf = kf1; the row's live entries are
+ * the one or two observations in ascending keyframe slot (the rule of the observation edits above), the rest of the row
+ * -1; mp_nobs = the sum over them of kf_uright >= 0 ? 2 : 1; kf_mappoint[kf1][idx1] = kf_mappoint[kf2][idx2] = p;
+ * mp_desc[p] = the kf_desc row of the first live entry whose keyframe is not bad (ComputeDistinctiveDescriptors for
+ * N <= 2, src/MapPoint.cc:300-314: both medians are 0), not written when there is none.  kf_bad NULL: none is bad.
+ * kf_desc / mp_desc, mp_normal and mp_max_min may be NULL (not written).
+ * Optional outputs: frame_mappoint[item_frame[i]][idx1] = p (an item_frame outside [0, n_frames) or idx1 >= kp_cap: not
+ * written); created [n_items][list_cap], -1 where no point was created, and n_created[i]; recent[n_recent[0] ..] gets the
+ * created slots in creation order and n_recent[0] advances (recentAddedMapPoints_.push_back, LocalMapping.cc:575).
+ * The same keypoint of one keyframe twice in a call: the host form refuses it; on the device form the result is
+ * unspecified, but every store stays inside its table.
+ * Intended range: a keyframe's batch (tens of items, hundreds to a few thousand points); the decision is one workgroup,
+ * serial in n_items * ceil(list_cap / 256) and in the slots taken.
+ * Workspace (per thread, grow-only): 4 * (n_items * ceil(list_cap / 256) + 5) bytes.
+ * ---------------------------------------------------------------------------------------- */
+#define ORBMK_OK 0
+#define ORBMK_OVERFLOW 1
+
+typedef struct orbmk_frames {
+    int32_t n_frames, kp_cap;
+    const int32_t* frame_n;           /* [F] */
+    const int32_t* frame_mappoint;    /* [F][kp_cap] */
+    const orbx_keypoint* kp_un;       /* [F][kp_cap] keypointsUn (orbfr_frames.kp_un) */
+    const int32_t* kp_octave;         /* [F][kp_cap] */
+    const float* kp_uright;           /* [F][kp_cap] */
+    const float* kp_depth;            /* [F][kp_cap] */
+    const uint8_t* kp_desc;           /* [F][kp_cap][32], 16-byte aligned */
+    const float* pose;                /* [F][12] */
+    const float* camera;              /* [F][5] fx, fy, cx, cy, bf */
+} orbmk_frames;
+
+typedef struct orbmk_keyframes {      /* every pointer optional */
+    int32_t n_keyframes, kf_cap, conn_cap;
+    int32_t* kf_id;                   /* [K] */
+    int32_t* kf_n;                    /* [K] */
+    int32_t* kf_mappoint;             /* [K][kf_cap] */
+    orbx_keypoint* kf_keypoint;       /* [K][kf_cap] */
+    int32_t* kf_kp_octave;            /* [K][kf_cap] */
+    float* kf_uright;                 /* [K][kf_cap] */
+    float* kf_depth;                  /* [K][kf_cap] */
+    uint8_t* kf_desc;                 /* [K][kf_cap][32], 16-byte aligned */
+    float* kf_pose;                   /* [K][12] */
+    float* kf_camera;                 /* [K][6] fx, fy, cx, cy, bf, baseline */
+    uint8_t* kf_bad; uint8_t* kf_not_erase; uint8_t* kf_to_be_erased;   /* [K] */
+    int32_t* kf_parent;               /* [K] */
+    uint8_t* kf_first_connection;     /* [K] */
+    int32_t* conn_slot; int32_t* conn_weight; int32_t* n_conn;          /* orbmm_graph's */
+    int32_t* ord_slot; int32_t* ord_weight; int32_t* n_ord;
+    int32_t* kf_covis;                /* [K][ORBDB_COVIS] */
+} orbmk_keyframes;
+
+typedef struct orbmk_map {
+    int32_t n_keyframes, n_mappoints, kf_cap;
+    int32_t n_obs;                    /* entries of mp_obs_kf / mp_obs_idx (>= mp_obs_off[n_mappoints]) */
+    const int32_t* kf_id;             /* [K] */
+    const int32_t* kf_n;              /* [K] */
+    int32_t*       kf_mappoint;       /* [K][kf_cap] updated */
+    const float*   kf_uright;         /* [K][kf_cap] */
+    const uint8_t* kf_bad;            /* [K] optional */
+    const uint8_t* kf_desc;           /* [K][kf_cap][32] optional, with mp_desc */
+    uint8_t*       mp_bad;            /* [M] */
+    float*         mp_xw;             /* [M][3] */
+    float*         mp_normal;         /* [M][3] optional */
+    float*         mp_max_min;        /* [M][2] optional */
+    int32_t*       mp_nobs;           /* [M] */
+    int32_t*       mp_found;          /* [M] */
+    int32_t*       mp_visible;        /* [M] */
+    int32_t*       mp_replaced;       /* [M] */
+    int32_t*       mp_first_kf_id;    /* [M] */
+    int32_t*       mp_ref_kf;         /* [M] */
+    uint8_t*       mp_desc;           /* [M][32] optional, 16-byte aligned */
+    const int32_t* mp_obs_off;        /* [M + 1] */
+    int32_t*       mp_obs_kf;
+    int32_t*       mp_obs_idx;
+} orbmk_map;
+
+typedef struct orbmk_lists {
+    int32_t n_items, list_cap;
+    int32_t values_by_keypoint;       /* 0: the values of entry (i, j) at row i * list_cap + j; 1: at i * list_cap + idx1 */
+    const int32_t* kf1;               /* [n_items] */
+    const int32_t* kf2;               /* [n_items] or NULL */
+    const int32_t* n_list;            /* [n_items] */
+    const int32_t* idx1;              /* [n_items][list_cap] */
+    const int32_t* idx2;              /* [n_items][list_cap]; required with kf2 */
+    const float* xw;                  /* [n_items][list_cap][3] */
+    const float* normal;              /* [n_items][list_cap][3] or NULL */
+    const float* max_distance;        /* [n_items][list_cap] or NULL */
+    const float* min_distance;        /* [n_items][list_cap] or NULL */
+    int32_t n_frames, kp_cap;         /* of frame_mappoint; ignored when that is NULL */
+    const int32_t* item_frame;        /* [n_items]; required with frame_mappoint */
+    int32_t* frame_mappoint;          /* [n_frames][kp_cap] or NULL; updated */
+} orbmk_lists;
+
+typedef struct orbmk_created {
+    int32_t* alloc;                   /* [1] input and output */
+    int32_t* status;                  /* [1] ORBMK_* */
+    int32_t* needed;                  /* [2] */
+    int32_t* created;                 /* [n_items][list_cap] or NULL */
+    int32_t* n_created;               /* [n_items] or NULL */
+    int32_t* recent;                  /* [recent_cap] or NULL */
+    int32_t* n_recent;                /* [1] input and output; required with recent */
+    int32_t recent_cap;
+} orbmk_created;
+
+/* Device forms: every array in HBM (the structs themselves are host memory); enqueue only on `stream`, nothing is copied
+ * back.  ORB_EINVAL for a NULL struct or required array, negative sizes, kp_cap, kf_cap or list_cap < 1, kp_cap > kf_cap,
+ * conn_cap < 1 with a connection row given, 65536 items or more, a table of 2^31 entries or more, descriptors not 16-byte
+ * aligned (device forms), kf_desc without mp_desc or the reverse, values_by_keypoint not 0 or 1.  The workspace belongs to the calling
+ * thread: its calls must be stream-ordered. */
+int orbmk_insert_keyframes_device(const orbmk_frames* frames, const orbmk_keyframes* keyframes, int32_t n_items,
+                                  const int32_t* item_frame, const int32_t* item_kf, const int32_t* item_id,
+                                  const float* item_baseline, void* stream);
+int orbmk_create_points_device(const orbmk_map* map, const orbmk_lists* lists, const orbmk_created* out, void* stream);
+/* Host forms: every pointer is host memory, synchronous; the updated arrays are written back.  Before anything is
+ * copied, besides the checks above: item_frame in [0, n_frames), item_kf in [0, n_keyframes) and no slot twice, frame_n
+ * in [0, kp_cap]; the offsets start at 0, do not decrease and end within n_obs, kf_n in [0, kf_cap], kf1 in
+ * [0, n_keyframes), kf2 in [-1, n_keyframes), n_list in [0, list_cap], idx1 and idx2 in [-1, kf_cap) (-1: no entry),
+ * the lists' item_frame in [-1, n_frames), alloc[0] in [0, n_mappoints], n_recent[0] in [0, recent_cap], no keypoint of
+ * a keyframe twice among the valid entries.  ORB_EINVAL otherwise. */
+int orbmk_insert_keyframes(const orbmk_frames* frames, const orbmk_keyframes* keyframes, int32_t n_items,
+                           const int32_t* item_frame, const int32_t* item_kf, const int32_t* item_id,
+                           const float* item_baseline, int device);
+int orbmk_create_points(const orbmk_map* map, const orbmk_lists* lists, const orbmk_created* out, int device);
 
 const char* orb_last_error(void);
 int orb_device_count(void);

@@ -984,6 +984,53 @@ private:
     int32_t* kp_begin_;
 };
 
+// Where the map grows (src/KeyFrame.cc:51-64, src/MapPoint.cc:44-56 with src/Tracking.cc:724-736, :981-997, :1104-1126 and
+// src/LocalMapping.cc:562-575): the host owns the slot tables in HBM and the KeyFrame* <-> slot table; it enqueues the KeyFrame
+// constructor for the frames it chose slots for, and the MapPoint constructor with AddObservation / AddMapPoint /
+// Map::AddMapPoint on the lists orbtf_stereo_points_device and orblm_create_new_map_points_device left in HBM, with the slots
+// allocated on the device.  Both only enqueue on `stream`; nothing is copied back.
+class MapBuilder {
+public:
+    MapBuilder(const orbmk_keyframes& keyframes, const orbmk_map& map) : keyframes_(keyframes), map_(map) {}
+
+    // d_item_*: [n_items] frame of `frames`, keyframe slot, KeyFrame::id, camera.baseline
+    void InsertKeyFrames(const orbmk_frames& frames, int32_t n_items, const int32_t* d_item_frame, const int32_t* d_item_kf,
+                         const int32_t* d_item_id, const float* d_item_baseline, void* stream = nullptr) const {
+        check(orbmk_insert_keyframes_device(&frames, &keyframes_, n_items, d_item_frame, d_item_kf, d_item_id, d_item_baseline, stream),
+              "orbmk_insert_keyframes_device");
+    }
+    // out.status[0] (HBM) is ORBMK_OK or ORBMK_OVERFLOW: read it when convenient
+    void CreatePoints(const orbmk_lists& lists, const orbmk_created& out, void* stream = nullptr) const {
+        check(orbmk_create_points_device(&map_, &lists, &out, stream), "orbmk_create_points_device");
+    }
+    // CreateMapPoints / StereoInitialization (src/Tracking.cc:724-736, :981-997): the lists orbtf_stereo_points_device wrote
+    // for `frames`, one observation in the keyframe d_item_kf[f]; frame_mappoint gets the new slots
+    void CreatePoints(const orbtf_frames& frames, const orbtf_created& created, const int32_t* d_item_kf,
+                      const int32_t* d_item_frame, const orbmk_created& out, void* stream = nullptr) const {
+        orbmk_lists l{};
+        l.n_items = frames.n_frames; l.list_cap = frames.kp_cap;
+        l.kf1 = d_item_kf; l.n_list = created.n_created; l.idx1 = created.created_kp; l.xw = created.created_xw;
+        l.n_frames = frames.n_frames; l.kp_cap = frames.kp_cap; l.item_frame = d_item_frame; l.frame_mappoint = frames.frame_mappoint;
+        CreatePoints(l, out, stream);
+    }
+    // CreateNewMapPoints (src/LocalMapping.cc:562-575): the lists orblm_create_new_map_points_device wrote for n_plan plan
+    // entries of keyframes d_kf1 / d_kf2 (slots), values by keypoint; out.recent is recentAddedMapPoints_
+    void CreatePoints(const orblm_points& points, int32_t n_plan, int32_t cap1, const int32_t* d_kf1, const int32_t* d_kf2,
+                      const orbmk_created& out, void* stream = nullptr) const {
+        orbmk_lists l{};
+        l.n_items = n_plan; l.list_cap = cap1; l.values_by_keypoint = 1;
+        l.kf1 = d_kf1; l.kf2 = d_kf2; l.n_list = points.n_created; l.idx1 = points.new_idx1; l.idx2 = points.new_idx2;
+        l.xw = points.xw; l.normal = points.normal; l.max_distance = points.max_distance; l.min_distance = points.min_distance;
+        CreatePoints(l, out, stream);
+    }
+    const orbmk_keyframes& keyframes() const { return keyframes_; }
+    const orbmk_map& map() const { return map_; }
+
+private:
+    orbmk_keyframes keyframes_;
+    orbmk_map map_;
+};
+
 // Map maintenance (src/MapPoint.cc:341-380, src/KeyFrame.cc:94-119, 235-309): the host owns the arrays of orbmm_graph in
 // HBM; after the map moved on the device (orbba_gba_update_map_device, the essential graph, new points, Fuse) it enqueues
 // UpdateNormalAndDepth for the points and UpdateConnections for the keyframes on the stream the readers follow on

@@ -37,6 +37,10 @@ Host mirrors of the reference's interfaces (tiantianxuabc/ORB_SLAM2_Refactored):
   frame                           <- what System does between Extract and the Frame constructor (src/System.cc:153-219):
                                      UndistortKeyPoints, ComputeImageBounds, depth.convertTo + ComputeStereoFromRGBD and the
                                      split of cv::KeyPoint into tracking's arrays: build, build_device, frame.py
+  InsertKeyFrames / CreatePoints  <- where the map grows: the KeyFrame constructor (src/KeyFrame.cc:51-64) and the MapPoint
+                                     constructor with AddObservation / AddMapPoint / Map::AddMapPoint (src/MapPoint.cc:44-56,
+                                     src/Tracking.cc:724-736, :981-997, :1104-1126, src/LocalMapping.cc:562-575) on the slot
+                                     tables, with the slot allocation, creation.py
 All compute runs in liborbslam2_amd.so (HIP kernels behind include/orbslam2_amd.h).
 """
 from .extractor import ORBextractor, KP_DTYPE
@@ -59,9 +63,10 @@ from .culling import (MapPointCulling, map_point_culling_device, KeyFrameCulling
                       CompactObservations, compact_observations_device, LiveChildren, live_children_device)
 from .observations import (AddKeyFrameObservations, add_keyframe_observations_device, FuseApply, fuse_apply_device,
                            GrowObservations, grow_observations_device)
+from .creation import InsertKeyFrames, insert_keyframes_device, CreatePoints, create_points_device
 from .synth import synth_image, shifted_pair, stereo_pair, make_pose_batch
 
-__all__ = ["AddKeyFrameObservations", "add_keyframe_observations_device", "FuseApply", "fuse_apply_device", "GrowObservations",
+__all__ = ["InsertKeyFrames", "insert_keyframes_device", "CreatePoints", "create_points_device", "AddKeyFrameObservations", "add_keyframe_observations_device", "FuseApply", "fuse_apply_device", "GrowObservations",
            "grow_observations_device", "MapPointCulling", "map_point_culling_device", "KeyFrameCulling", "keyframe_culling_device", "CompactObservations",
            "compact_observations_device", "LiveChildren", "live_children_device", "KeyFrameDatabase", "LocalMap", "UpdateNormalAndDepth", "update_normal_depth_device", "UpdateConnections",
            "update_connections_device", "Children", "children_device", "CovisCsr", "covis_csr_device", "PreparePairs", "TriangulateMatches", "CreateNewMapPoints", "prepare_pairs_device", "triangulate_matches_device",

@@ -369,6 +369,43 @@ class OrbfrFrames(C.Structure):
                                           "frame_mappoint", "frame_outlier", "kp_begin")]
 
 
+class OrbmkFrames(C.Structure):
+    """orbmk_frames (include/orbslam2_amd.h)."""
+    _fields_ = [("n_frames", C.c_int32), ("kp_cap", C.c_int32)] + [
+        (k, C.c_void_p) for k in ("frame_n", "frame_mappoint", "kp_un", "kp_octave", "kp_uright", "kp_depth", "kp_desc", "pose",
+                                  "camera")]
+
+
+class OrbmkKeyframes(C.Structure):
+    """orbmk_keyframes (include/orbslam2_amd.h)."""
+    _fields_ = [("n_keyframes", C.c_int32), ("kf_cap", C.c_int32), ("conn_cap", C.c_int32)] + [
+        (k, C.c_void_p) for k in ("kf_id", "kf_n", "kf_mappoint", "kf_keypoint", "kf_kp_octave", "kf_uright", "kf_depth", "kf_desc",
+                                  "kf_pose", "kf_camera", "kf_bad", "kf_not_erase", "kf_to_be_erased", "kf_parent",
+                                  "kf_first_connection", "conn_slot", "conn_weight", "n_conn", "ord_slot", "ord_weight", "n_ord",
+                                  "kf_covis")]
+
+
+class OrbmkMap(C.Structure):
+    """orbmk_map (include/orbslam2_amd.h)."""
+    _fields_ = [("n_keyframes", C.c_int32), ("n_mappoints", C.c_int32), ("kf_cap", C.c_int32), ("n_obs", C.c_int32)] + [
+        (k, C.c_void_p) for k in ("kf_id", "kf_n", "kf_mappoint", "kf_uright", "kf_bad", "kf_desc", "mp_bad", "mp_xw", "mp_normal",
+                                  "mp_max_min", "mp_nobs", "mp_found", "mp_visible", "mp_replaced", "mp_first_kf_id", "mp_ref_kf",
+                                  "mp_desc", "mp_obs_off", "mp_obs_kf", "mp_obs_idx")]
+
+
+class OrbmkLists(C.Structure):
+    """orbmk_lists (include/orbslam2_amd.h)."""
+    _fields_ = [("n_items", C.c_int32), ("list_cap", C.c_int32), ("values_by_keypoint", C.c_int32)] + [
+        (k, C.c_void_p) for k in ("kf1", "kf2", "n_list", "idx1", "idx2", "xw", "normal", "max_distance", "min_distance")] + [
+        ("n_frames", C.c_int32), ("kp_cap", C.c_int32), ("item_frame", C.c_void_p), ("frame_mappoint", C.c_void_p)]
+
+
+class OrbmkCreated(C.Structure):
+    """orbmk_created (include/orbslam2_amd.h)."""
+    _fields_ = [(k, C.c_void_p) for k in ("alloc", "status", "needed", "created", "n_created", "recent", "n_recent")] + [
+        ("recent_cap", C.c_int32)]
+
+
 class OrbmmPoints(C.Structure):
     """orbmm_points (include/orbslam2_amd.h)."""
     _fields_ = [("n_keyframes", C.c_int32), ("n_mappoints", C.c_int32), ("kf_cap", C.c_int32), ("n_obs", C.c_int32),
@@ -602,6 +639,10 @@ SIGNATURES = {    "orbx_create": (C.c_int, [C.POINTER(OrbxParams), C.c_int, C.PO
     "orbfr_build_frames": (C.c_int, [C.POINTER(OrbfrInput), C.POINTER(OrbfrFrames), C.c_int]),
     "orbfr_image_bounds": (C.c_int, [C.c_int32, C.c_int32, VP, VP, VP]),
     "orbfr_undistort_points": (C.c_int, [VP, VP, VP, C.c_int32, VP]),
+    "orbmk_insert_keyframes_device": (C.c_int, [C.POINTER(OrbmkFrames), C.POINTER(OrbmkKeyframes), C.c_int32, VP, VP, VP, VP, VP]),
+    "orbmk_insert_keyframes": (C.c_int, [C.POINTER(OrbmkFrames), C.POINTER(OrbmkKeyframes), C.c_int32, VP, VP, VP, VP, C.c_int]),
+    "orbmk_create_points_device": (C.c_int, [C.POINTER(OrbmkMap), C.POINTER(OrbmkLists), C.POINTER(OrbmkCreated), VP]),
+    "orbmk_create_points": (C.c_int, [C.POINTER(OrbmkMap), C.POINTER(OrbmkLists), C.POINTER(OrbmkCreated), C.c_int]),
     "orbx_profile_enable": (C.c_int, [VP, C.c_int]),
     "orbx_profile_read": (C.c_int, [VP, VP, VP]),
     "orbx_debug_level_candidates": (C.c_int, [VP, C.c_int, C.c_int, VP, C.c_int, C.POINTER(C.c_int)]),
