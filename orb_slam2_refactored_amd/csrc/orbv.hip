@@ -15,7 +15,8 @@
 //                         first closest child as the reference's strict-< scan, one level per step;
 //                         records the node at level L - levelsup.
 //   voc_aggregate_kernel  one workgroup per frame: bitonic sorts of (word, feature) and (node, feature)
-//                         in LDS; per word the weight added in feature order (the map's += sequence),
+//                         in LDS; per word each feature's own weight added in feature order (the map's +=
+//                         sequence; nodes that share a word id may differ in weight),
 //                         the L1 / L2 norm summed in word order by one lane, then the division;
 //                         FeatureVector as CSR.
 #include <algorithm>
@@ -180,10 +181,18 @@ __global__ __launch_bounds__(256) void voc_aggregate_kernel(VocFeat ft, const in
     for (int p = threadIdx.x; p < P; p += 256) {
         if (!is_start(p)) continue;
         const uint32_t w = (uint32_t)(s_keys[p] >> 32);
-        const double wt = ft.weight[base + (unsigned)(s_keys[p] & 0xffffffffu)];   // the word node's weight
-        double val = wt;
-        if (tf)   // v[id] += w once per further feature, in feature order
-            for (int q = p + 1; q < P && s_keys[q] != ~0ull && (uint32_t)(s_keys[q] >> 32) == w; q++) val += wt;
+        const auto same = [&](int q) { return q < P && s_keys[q] != ~0ull && (uint32_t)(s_keys[q] >> 32) == w; };
+        const auto own = [&](int q) { return ft.weight[base + (unsigned)(s_keys[q] & 0xffffffffu)]; };
+        // v[id] += each further feature's own w, in feature order: two nodes can share a word id (a childless
+        // node the file flags "not a leaf" keeps word_id = 0) and need not share a weight.  The second feature's
+        // load goes out with the first's, so a word of two features (the usual repeat) waits for memory once.
+        const bool two = tf && same(p + 1);
+        double val = own(p);   // the word's first feature
+        if (two) {
+            const double second = own(p + 1);
+            val += second;
+            for (int q = p + 2; same(q); q++) val += own(q);
+        }
         s_val[s_pos[p]] = val;
         o.bow_word[base + s_pos[p]] = w;
     }
